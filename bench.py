@@ -10,10 +10,20 @@ maps [4, 32, 136, 240] x 2) are resident in HBM before the timed region.  Pairs 
 the reference shards them (pair i -> rank i mod world, tools/test.py:108); the only collective is ONE SUM
 all-reduce of the FP64 EPE accumulator over RCCL at the end of the job (inside the timed region).
 
-Prints ONE JSON line (rank 0).  ``roofline`` is for the dominant kernel (conv3d k3 s1 32->32, FP32 MFMA bound):
-algorithmic FLOP per launch / mean launch duration measured live with HIP events on the launch stream.
-``cpu_baseline`` times the CPU oracle (a port of the reference's PyTorch-CPU path) on the host: 1 warm-up + 3 timed full-size
-pairs.
+Prints ONE JSON line (rank 0): ``value`` pairs/s and ``ms_per_step`` over the ``--steps`` timed steps.  A plain run does only
+that: set up, ``--warmup`` untimed steps, the timed steps, ``--dump-outputs``, the line.
+
+``--dump-outputs DIR`` writes what the last timed step computed -- the arrays a caller of the path receives (``disp<i>``,
+``cost<i>``, ``conf<i>`` in the order of the model's result lists, FP32) and the FP64 EPE accumulator of the timed steps
+(``epe_accumulator``) -- as DIR/<name>.npy, 60 MiB at most: an array above its share is written as a fixed, seeded sample of its
+flattened elements.  The inputs are seeded, so two builds given the same arguments can be compared output for output.
+
+``--full`` adds everything else (secondary figures, each after the timed region): ``roofline`` for the dominant kernel (conv3d
+k3 s1 32->32, FP32 MFMA bound): algorithmic FLOP per launch / mean launch duration measured live with HIP events on the launch
+stream inside the timed region; ``cpu_baseline`` times the CPU oracle (a port of the reference's PyTorch-CPU path) on the host:
+1 warm-up + 3 timed full-size pairs, with the parity of pair 0 against it; the batch-1 latency legs,
+the backbone end to end, the opt-in modes and the training step.  ``--no-cpu-baseline``, ``--no-extras``, ``--latency`` and
+``--no-latency`` select among them.
 """
 import argparse
 import json
@@ -56,13 +66,18 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=4, help="stereo pairs per GPU per step (cfg2: 4)")
     ap.add_argument("--config", default=os.path.join(ROOT, "configs", "PSMNet", "scene_flow.py"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary legs (backbone, bf16x6, training step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs and the EPE accumulator as DIR/<name>.npy (60 MiB at most)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline: roofline, CPU baseline + parity, latency, "
+                         "backbone, opt-in modes, training step")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) no CPU baseline and parity check")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the secondary legs (backbone, bf16x6, training step)")
     ap.add_argument("--conv3d-mode", default="exact", choices=["exact", "bf16x6"],
                     help="opt-in EXPERIMENT: 32-channel stride-1 layers on 3-way bf16 splits (FP32-equivalent accuracy, not "
                          "bit-identical); the headline is always measured with 'exact'")
-    ap.add_argument("--latency", action="store_true", help="add the batch-1 latency legs (implied by --batch 1)")
-    ap.add_argument("--no-latency", action="store_true", help="no latency legs even at --batch 1 (profiling runs)")
+    ap.add_argument("--latency", action="store_true", help="(--full) add the batch-1 latency legs (implied by --batch 1)")
+    ap.add_argument("--no-latency", action="store_true", help="(--full) no latency legs even at --batch 1 (profiling runs)")
     ap.add_argument("--fused-regression", action="store_true",
                     help="opt-in fast path: fused up-sampling + soft-argmin, full-resolution costs not materialised")
     return ap.parse_args()
@@ -421,6 +436,66 @@ def training_leg(cfg, dev, steps):
     return out
 
 
+def roofline(timer, B, d4, h4, w4, conv3d_mode):
+    """(--full) The dominant kernel's launches as timed live in the timed region (``timer``) against the FP32 matrix peak."""
+    kms = timer.mean_ms(DOMINANT)
+    flop = 2.0 * 27 * 32 * 32 * B * d4 * h4 * w4
+    achieved = flop / (kms * 1e-3) / 1e12
+    # `traffic` is NOT measured by this run: it is the PMC figure (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the same
+    # command, scripts/profile.sh) of the tracked profile summary, valid for the workload that summary was taken on
+    traffic, traffic_source = None, None
+    import glob
+    for pmc in sorted(glob.glob(os.path.join(ROOT, "profiles", "pmc_dominant*.json")), reverse=True):   # one summary per profiled workload
+        try:
+            rec = json.load(open(pmc))
+            if tuple(rec.get("shape", [])) == (B, 32, d4, h4, w4):
+                traffic = rec.get("hbm_bytes_per_launch")
+                traffic_source = "profiles/%s (rocprofv3 PMC passes of an earlier run of this command: %s)" % (
+                    os.path.basename(pmc), rec.get("derived_from", "see the file"))
+                break
+        except Exception:  # noqa: BLE001
+            continue
+    out = {"kernel": "conv3d_s1_kernel<32,32> (k3 s1 32->32, [%d,32,%d,%d,%d])" % (B, d4, h4, w4),
+           "bound": "mfma", "achieved": round(achieved, 2), "peak": PEAK_FP32_MFMA_TFLOPS,
+           "unit": "TFLOP/s", "frac": round(achieved / PEAK_FP32_MFMA_TFLOPS, 4), "traffic": traffic,
+           "traffic_source": traffic_source,
+           "launch_ms": round(kms, 4), "launches_timed": timer.count(DOMINANT),
+           "timed_every_nth_step": timer.every,
+           "flop_per_launch": flop}
+    if conv3d_mode != "exact":   # the split kernel issues 6 bf16 MFMAs per FP32 product (+ 28/27 tap padding)
+        issued = achieved * 6.0 * 28.0 / 27.0
+        out.update({"kernel": "conv3d_s1_x6_kernel (k3 s1 32->32, bf16x6 split)", "achieved": round(issued, 1),
+                    "peak": 2500.0, "frac": round(issued / 2500.0, 4),
+                    "fp32_equivalent_tflops": round(achieved, 2), "traffic": None})
+    return out
+
+
+DUMP_BUDGET_BYTES = 60 * 2 ** 20
+
+
+def dump_outputs(directory, arrays):
+    """``arrays`` (name -> tensor) as ``directory``/<name>.npy: FP64 tensors as FP64, everything else as FP32, DUMP_BUDGET_BYTES in
+    all.  Smallest first, each array gets an equal share of what is left; one that is larger is written as the elements at a
+    fixed, seeded sample of its flattened indices (sorted: the same positions in every run and every build).  The sample is drawn
+    by numpy on the host: torch.randperm of a few million elements took 15 s per call in a process that had run the path."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    left, samples = DUMP_BUDGET_BYTES, {}
+    for n, name in enumerate(sorted(host, key=lambda k: host[k].nbytes)):
+        a = host[name]
+        cap = left // (len(host) - n) // a.itemsize
+        if a.size > cap:
+            if (a.size, cap) not in samples:
+                samples[(a.size, cap)] = np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))
+            a = a.reshape(-1)[samples[(a.size, cap)]]
+        np.save(os.path.join(directory, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def pin_to_gpu_numa_node(local_rank):
     """Bind this rank's host threads to the CPUs of the NUMA node its GPU hangs off (the reference leaves placement to the OS;
     with eight ranks on a two-socket host a rank whose launch thread runs on the far socket pays a cross-socket hop per launch).
@@ -539,7 +614,8 @@ def main():
 
     last_results = {}
 
-    def step(k=None, fused=fused):
+    def step(k=None, fused=fused, keep=False):
+        """One step; ``keep``: hold on to everything the model returned (the last timed step, for --dump-outputs)."""
         if k is None:
             k = counter[0]
             counter[0] += 1
@@ -549,7 +625,7 @@ def main():
             results, _ = model(batch)
             disps = results["disps"]
             last_results.clear()
-            last_results.update({k: v for k, v in results.items() if k == "confs"})
+            last_results.update({name: v for name, v in results.items() if keep or name == "confs"})
         else:
             agg = model.cost_processor.aggregator
             if ops.cat_fusion() and ptype == "Concatenation":   # the volume-free first layer, as the default mode runs it
@@ -575,17 +651,19 @@ def main():
             disps = step()
         acc.acc.zero_()
         counter[0] = 0
-        # live HIP-event timing of the dominant kernel's launches inside the timed region: every launch of every step for short
-        # runs, of every (steps / 4)-th step from 16 steps on (>= 24 timed launches either way; each bracketed launch costs its stream ~10 us)
-        # (round 6: every (steps / 4)-th step = 24 timed launches of a PSMNet step's six -- at one 256x512 pair the 10 us per bracketed
-        # launch were 1.5 % of the step when every 4th step was timed)
-        timer = ops.KernelTimer([DOMINANT], every=max(1, args.steps // 4) if args.steps >= 16 else 1)
+        # --full: live HIP-event timing of the dominant kernel's launches inside the timed region: every launch of every step for
+        # short runs, of every (steps / 4)-th step from 16 steps on (>= 24 timed launches either way; each bracketed launch costs its
+        # stream ~10 us) (round 6: every (steps / 4)-th step = 24 timed launches of a PSMNet step's six -- at one 256x512 pair the
+        # 10 us per bracketed launch were 1.5 % of the step when every 4th step was timed).  A plain run brackets nothing.
+        timer = ops.KernelTimer([DOMINANT], every=max(1, args.steps // 4) if args.steps >= 16 else 1) if args.full else None
         ops.set_kernel_timer(timer)
+        dump = args.dump_outputs is not None and rank == 0
         fence()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            timer.begin_step()
-            disps = step()
+        for i in range(args.steps):
+            if timer is not None:
+                timer.begin_step()
+            disps = step(keep=dump and i == args.steps - 1)
         acc.all_reduce()
         fence()
         elapsed = time.perf_counter() - t0
@@ -603,25 +681,17 @@ def main():
     value = pairs / elapsed
     metrics = acc.summary()
 
+    if dump:   # (rank 0) what the last timed step returned, and the accumulator of all timed steps
+        arrays = {"disp%d" % i: d for i, d in enumerate(disps)}
+        for key in ("costs", "confs"):
+            arrays.update({"%s%d" % (key[:-1], i): t for i, t in enumerate(last_results.get(key) or []) if torch.is_tensor(t)})
+        arrays["epe_accumulator"] = acc.acc
+        dump_outputs(args.dump_outputs, arrays)
+        del arrays
+        last_results.pop("costs", None)
+
     if rank == 0:
-        kms = timer.mean_ms(DOMINANT)
         d4, h4, w4 = md // scale, fh, fw
-        flop = 2.0 * 27 * 32 * 32 * B * d4 * h4 * w4
-        achieved = flop / (kms * 1e-3) / 1e12
-        # `traffic` is NOT measured by this run: it is the PMC figure (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the same
-        # command, scripts/profile.sh) of the tracked profile summary, valid for the workload that summary was taken on
-        traffic, traffic_source = None, None
-        import glob
-        for pmc in sorted(glob.glob(os.path.join(ROOT, "profiles", "pmc_dominant*.json")), reverse=True):   # one summary per profiled workload
-            try:
-                rec = json.load(open(pmc))
-                if tuple(rec.get("shape", [])) == (B, 32, d4, h4, w4):
-                    traffic = rec.get("hbm_bytes_per_launch")
-                    traffic_source = "profiles/%s (rocprofv3 PMC passes of an earlier run of this command: %s)" % (
-                        os.path.basename(pmc), rec.get("derived_from", "see the file"))
-                    break
-            except Exception:  # noqa: BLE001
-                continue
         out = {
             "metric": "stereo pairs/s (%dx%d, max_disp=%d)" % (H0, W0, md), "value": round(value, 3), "unit": "pairs/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "pairs": pairs,
@@ -637,13 +707,6 @@ def main():
                             {"Concatenation": "2-D maps, volume not materialised (csrc/catconv.hip)",
                              "Difference": "2-D maps, volume not materialised (csrc/catconv.hip)",
                              "Correlation": "correlation channels 3-D, concat channels as 2-D maps (csrc/catconv.hip)"}.get(ptype, "3-D convolution")),
-            "roofline": {"kernel": "conv3d_s1_kernel<32,32> (k3 s1 32->32, [%d,32,%d,%d,%d])" % (B, d4, h4, w4),
-                         "bound": "mfma", "achieved": round(achieved, 2), "peak": PEAK_FP32_MFMA_TFLOPS,
-                         "unit": "TFLOP/s", "frac": round(achieved / PEAK_FP32_MFMA_TFLOPS, 4), "traffic": traffic,
-                         "traffic_source": traffic_source,
-                         "launch_ms": round(kms, 4), "launches_timed": timer.count(DOMINANT),
-                         "timed_every_nth_step": timer.every,
-                         "flop_per_launch": flop},
             "epe_accumulator": metrics[0],
             "per_rank_ms": [round(t, 3) for t in per_rank_ms],
             "host_affinity": affinity,
@@ -671,16 +734,14 @@ def main():
             # the path is compute-bound, the FP32 matrix peak caps this fraction at 0.188)
             out["path_hbm_gbs_algorithmic"] = round(value * gb, 1)
             out["path_frac_hbm_roofline"] = round(value * gb / world / PEAK_HBM_GBS, 4)
-        if args.conv3d_mode != "exact":   # the split kernel issues 6 bf16 MFMAs per FP32 product (+ 28/27 tap padding)
-            issued = achieved * 6.0 * 28.0 / 27.0
-            out["roofline"].update({"kernel": "conv3d_s1_x6_kernel (k3 s1 32->32, bf16x6 split)", "achieved": round(issued, 1),
-                                    "peak": 2500.0, "frac": round(issued / 2500.0, 4),
-                                    "fp32_equivalent_tflops": round(achieved, 2), "traffic": None})
+        if args.full:
+            out["roofline"] = roofline(timer, B, d4, h4, w4, args.conv3d_mode)
         agg_type = cfg.model.cost_processor.cost_aggregator.type
         out["distinct_pairs_per_gpu"] = nb * B
-        with torch.no_grad():
-            disps = step(0)      # batch 0 again: the parity check and the secondary legs below all look at global pair 0
-        if not args.no_cpu_baseline:
+        if args.full:
+            with torch.no_grad():
+                disps = step(0)      # batch 0 again: the parity check and the secondary legs below all look at global pair 0
+        if args.full and not args.no_cpu_baseline:
             first = tuple(t[0:1].cpu() for t in left) if isinstance(left, tuple) else left[0:1].cpu()
             first_r = tuple(t[0:1].cpu() for t in right) if isinstance(right, tuple) else right[0:1].cpu()
             # BASELINE.md's protocol (1 warm-up + 3 timed pairs) at every N: the other ranks have left the timed region and wait at
@@ -728,10 +789,10 @@ def main():
                 if len(ref) > 2 and "confs" in last_results:
                     out["parity_vs_cpu"]["max_abs_conf"] = [round((a[0:1].cpu() - b).abs().max().item(), 7)
                                                             for a, b in zip(last_results["confs"], ref[2])]
-        if world == 1 and (B == 1 or args.latency) and not args.no_latency and not fused and args.conv3d_mode == "exact":
+        if args.full and world == 1 and (B == 1 or args.latency) and not args.no_latency and not fused and args.conv3d_mode == "exact":
             # the batch-1 / serving regime (dmb/apis/inference.py:191-225): ms per pair, eager and replayed from a HIP graph
             out["latency"] = latency_leg(cfg, model, dev, batches[0][0], H0, W0, Hp, Wp, min(args.steps, 20))
-        if world == 1 and ptype == "Concatenation" and agg_type == "PSMNet" and not fused and not args.no_extras:
+        if args.full and world == 1 and ptype == "Concatenation" and agg_type == "PSMNet" and not fused and not args.no_extras:
             out["end_to_end_with_backbone"] = end_to_end(cfg, model, dev, B, H0, W0, Hp, Wp, min(args.steps, 5), check=not args.no_cpu_baseline)
             if args.conv3d_mode == "exact":
                 out["opt_in_branch_overlap"] = overlap_leg(lambda: step(0), disps, B, min(args.steps, 10))

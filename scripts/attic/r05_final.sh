@@ -9,7 +9,7 @@ if [ "$1" = "1" ]; then
   tail -4 $O/pytest.log
   timeout 1500 bash scripts/bench_configs.sh > $O/configs.log 2> $O/configs.err
   wc -l $O/configs.log
-  timeout 300 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+  timeout 300 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
   tail -c 600 $O/bench.json
 else
   bash scripts/profile.sh r05 > $O/profile_r05.log 2>&1

@@ -8,7 +8,7 @@ timeout 900 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "pyte
 tail -5 $O/pytest.log
 timeout 900 bash scripts/bench_b1.sh > $O/b1.log 2> $O/b1.err
 cat $O/b1.log | cut -c1-1500
-timeout 300 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
 for c in PSMNet/baseline_cfg0_256x512_d64.py PSMNet/scene_flow.py; do
   t=$(basename $c .py)

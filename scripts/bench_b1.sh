@@ -5,5 +5,5 @@
 R=$GRAFT_REPO_ROOT
 cd $R
 for c in PSMNet/baseline_cfg0_256x512_d64.py PSMNet/scene_flow.py PSMNet/kitti_2015.py AcfNet/kitti_2015_adaptive.py; do
-  python bench.py --config $R/configs/$c --batch 1 --steps 40 --warmup 10 --no-extras 2>/dev/null | tail -1
+  python bench.py --config $R/configs/$c --batch 1 --steps 40 --warmup 10 --full --no-extras 2>/dev/null | tail -1
 done

@@ -10,7 +10,7 @@ if [ "$1" = "1" ]; then
   tail -4 $O/pytest.log
   timeout 1800 bash scripts/bench_configs.sh > $O/configs.log 2> $O/configs.err
   wc -l $O/configs.log
-  timeout 400 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+  timeout 400 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
   tail -c 400 $O/bench.json
 else
   bash scripts/profile.sh r06 > $O/profile_r06.log 2>&1

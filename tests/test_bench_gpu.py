@@ -60,3 +60,26 @@ def test_bench_one_rank_through_rccl(dev):
         assert rccl["epe_accumulator"][k] == plain["epe_accumulator"][k]
     assert rccl["value"] > 0
     assert rccl.get("rccl_version") and "rccl_version" not in plain     # e.g. "2.26.6": read from the library the job ran on
+
+
+def test_bench_dump_outputs(dev, tmp_path):
+    """``--dump-outputs DIR``: the last timed step's arrays (disparity maps, cost volumes -- sampled above their share) and the FP64
+    EPE accumulator, FP32 / FP64, 64 MB at most; the same arguments give the same outputs, with or without ``--full`` (whose live
+    kernel timer brackets launches in the timed region but changes no result).  A plain line carries no secondary figure."""
+    import numpy as np
+    a, b = tmp_path / "plain", tmp_path / "full"
+    plain = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "1", "--dump-outputs", str(a))
+    full = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "1", "--dump-outputs", str(b), "--full", "--no-latency")
+    assert "roofline" not in plain and "latency" not in plain and "roofline" in full
+    assert plain["steps"] == full["steps"] == 3 and plain["ms_per_step"] > 0 and plain["pairs"] == 3
+    names = sorted(os.listdir(a))
+    assert names == sorted(os.listdir(b))
+    assert {"disp0.npy", "disp1.npy", "disp2.npy", "cost0.npy", "cost1.npy", "cost2.npy", "epe_accumulator.npy"} <= set(names)
+    assert sum(os.path.getsize(a / n) for n in names) <= 64 * 2 ** 20
+    for n in names:
+        x, y = np.load(a / n), np.load(b / n)
+        assert x.dtype in (np.float32, np.float64) and x.shape == y.shape and np.array_equal(x, y), n
+    assert np.load(a / "disp0.npy").shape[-2:] == (544, 960)
+    acc = np.load(a / "epe_accumulator.npy")
+    assert acc.dtype == np.float64 and acc[0, 0] == 3            # three timed steps of one pair each
+    assert abs(acc[0, 1] / acc[0, 0] - plain["epe_accumulator"]["epe"]) <= 1e-9 * max(1.0, plain["epe_accumulator"]["epe"])
