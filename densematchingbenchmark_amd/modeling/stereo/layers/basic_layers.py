@@ -24,6 +24,9 @@ def fold_batch_norm(bn, conv_bias, out_planes, device):
         if conv_bias is None:
             return None, None
         return torch.ones(out_planes, dtype=torch.float32, device=device), conv_bias.detach().float().contiguous()
+    if bn.running_mean is None or bn.running_var is None:
+        raise NotImplementedError("fold_batch_norm: a BatchNorm without running statistics (track_running_stats=False) "
+                                  "normalises with batch statistics in eval() too; it has no folded form")
     var = bn.running_var.detach().double()
     mean = bn.running_mean.detach().double()
     gamma = bn.weight.detach().double() if bn.affine else torch.ones_like(var)
@@ -84,6 +87,10 @@ class FusedConv3d(nn.Sequential):
         epoch_on_mode_switch(self, mode)
         return super().train(mode)
 
+    def _batch_stats(self):
+        """Training mode, or a BatchNorm that normalises with batch statistics in every mode (no running buffers)."""
+        return self.training or (self.has_bn and train_fn._batch_stats(self[1]))
+
     def _prepacked(self):
         conv = self[0]
         bn = self[1] if self.has_bn else None
@@ -104,7 +111,7 @@ class FusedConv3d(nn.Sequential):
         act = self.has_relu if relu is None else relu
         if getattr(x, "kind", None) == "gwc_cat":   # LazyGwcCatVolume: correlation channels 3-D, concat channels as 2-D maps
             G = x.num_groups
-            if (residual is None and skip is None and not self.transposed and self.stride == 1 and not self.training
+            if (residual is None and skip is None and not self.transposed and self.stride == 1 and not self._batch_stats()
                     and x.shape[1] == self.in_planes and G % 2 == 0 and self.out_planes == 32
                     and ops.catconv_applicable(x.reference_fm, x.target_fm, x.disp_idx, self.out_planes)):
                 key = _versions(self[0].weight)
@@ -123,7 +130,7 @@ class FusedConv3d(nn.Sequential):
             if (residual is None and skip is None and not self.transposed and self.stride == 1
                     and x.shape[1] == self.in_planes
                     and ops.catconv_applicable(x.reference_fm, x.target_fm, x.disp_idx, self.out_planes)):
-                if getattr(x, "differentiable", False) or self.training:
+                if getattr(x, "differentiable", False) or self._batch_stats():
                     # training path: the 2-D form in the forward pass, the volume only inside the backward pass
                     return train_fn.cat_conv_unit(self, x, act)
                 _, scale, shift = self._prepacked()

@@ -114,7 +114,8 @@ class _PackGroup:
     When to re-pack.  A weight's ``_version`` moving is one trigger, but torch's FUSED optimizers (``Adam(fused=True)``) update
     parameters without moving it -- so the group also counts passes: a unit asking for its packs a second time within one
     generation means a new forward pass has begun (every unit runs once per pass), the generation advances and everything is
-    re-packed, whatever the versions say.  One 19 us launch per pass either way."""
+    re-packed, whatever the versions say.  One 19 us launch per pass either way.  The parameter epoch, which every optimizer step
+    advances (ops.bump_param_epoch), is a third trigger: it also covers a unit that sat out the pass before the step."""
 
     def __init__(self, device):
         self.device, self.entries, self.table, self.njobs, self.gen = device, {}, None, 0, 0
@@ -124,14 +125,14 @@ class _PackGroup:
         if e is None or e["unit"]() is not unit or e["ptr"] != w.data_ptr() or e["shape"] != tuple(w.shape):
             jobs = ops.unit_pack_jobs(w, unit.transposed, unit.stride)
             e = {"unit": weakref.ref(unit), "ptr": w.data_ptr(), "shape": tuple(w.shape), "version": None, "seen": -1, "packed": -1,
-                 "jobs": jobs,
+                 "epoch": None, "jobs": jobs,
                  "bufs": [torch.empty((ops.packed_floats(co, ci),), dtype=torch.float32, device=w.device) for co, ci, _ in jobs]}
             self.entries[id(unit)] = e
             self.table = None
         if e["seen"] == self.gen:
             self.gen += 1                # second request within a generation: a new forward pass
         e["seen"] = self.gen
-        if e["packed"] != self.gen or e["version"] != w._version or self.table is None:
+        if e["packed"] != self.gen or e["version"] != w._version or e["epoch"] != ops.param_epoch() or self.table is None:
             self._repack(unit, w)
         return e["bufs"]
 
@@ -154,7 +155,7 @@ class _PackGroup:
         dead = False
         for e in self.entries.values():
             u = e["unit"]()
-            e["packed"] = self.gen
+            e["packed"], e["epoch"] = self.gen, ops.param_epoch()
             e["version"] = None if u is None else u[0].weight._version
             dead = dead or u is None
         if dead:
@@ -208,11 +209,17 @@ def set_epilogue_stats(flag):
     _epilogue_stats = bool(flag)
 
 
+def _batch_stats(bn):
+    """nn.BatchNorm's rule: batch statistics in training mode, and always for a BatchNorm that keeps no running buffers
+    (``track_running_stats=False``), whatever its mode."""
+    return bn is not None and (bn.training or bn.running_mean is None or bn.running_var is None)
+
+
 def _unit_bn_forward(bn, raw, gamma, beta, skip, code, C, device, partials=None):
     """BatchNorm (+ skip, + ReLU) of a unit's raw convolution output -> (y, mean, invstd, scale, shift, batch_stats).  A
     batch-statistics BatchNorm takes the two-launch form (ops.bn_train_fwd: block sums, then one kernel that finishes the
     statistics, updates the running buffers and the batch counter and normalises); running statistics / no BatchNorm: bn_act."""
-    if bn is not None and bn.training:
+    if _batch_stats(bn):
         if bn.momentum is None:   # nn.BatchNorm: cumulative moving average, factor 1 / (batches seen including this one)
             momentum = 1.0 / float(int(bn.num_batches_tracked) + 1) if bn.track_running_stats else 0.0
         else:
@@ -264,7 +271,7 @@ class ConvUnitFn(torch.autograd.Function):
         C = unit.out_planes
         bn = unit[1] if unit.has_bn else None
         partials = None
-        if (_epilogue_stats and bn is not None and bn.training and bias is None and not unit.transposed and unit.stride == 1 and C == 32):
+        if (_epilogue_stats and _batch_stats(bn) and bias is None and not unit.transposed and unit.stride == 1 and C == 32):
             # the statistics' block sums come out of the convolution's own epilogue (32-channel stride-1 units: 6 of PSMNet's 25)
             fused = ops.conv3d_k3_bnstats(x, wp_fwd, C)
             if fused is not None:
@@ -587,7 +594,7 @@ def _bn_forward(bn, training, raw, gamma, beta, C, device):
     train() whose BatchNorm layers were put in eval() -- fine-tuning with frozen statistics -- normalises with the running
     buffers and leaves them alone."""
     del training   # the enclosing unit's flag is not what decides
-    batch_stats = bn is not None and bn.training
+    batch_stats = _batch_stats(bn)
     if batch_stats:
         if bn.momentum is None:   # nn.BatchNorm: cumulative moving average, factor 1 / (batches seen including this one)
             momentum = 1.0 / float(int(bn.num_batches_tracked) + 1) if bn.track_running_stats else 0.0
@@ -631,7 +638,7 @@ def _phase_pack(unit, w, forward):
     d[other] = None
     c = d.get(mine)
     if c is None or c[0] != key or not _pack_group_enabled or torch.cuda.is_current_stream_capturing():
-        c = (key, ops.pack_conv2d_weights(w) if forward else ops.conv2d_dgrad_packs(w))
+        c = (key, ops.pack_conv2d_weights(w) if forward else ops.conv2d_dgrad_packs(w, unit.dilation))
         d[mine] = c
     return c[1]
 
@@ -648,8 +655,8 @@ class Conv2dUnitFn(torch.autograd.Function):
         w = weight.detach().contiguous()
         C, k, s, d = unit.out_planes, unit.kernel_size, unit.stride, unit.dilation
         if k == 5:
-            if s != 2 or d != 1 or x.shape[2] % 2 or x.shape[3] % 2:
-                raise NotImplementedError("training path of FusedConv2d: 5x5 layers are stride 2 on even input sizes")
+            if s != 2 or d != 1:
+                raise NotImplementedError("training path of FusedConv2d: 5x5 layers are stride 2")
         elif k not in (1, 3) or d not in (1, 2, 4, 8) or (s == 2 and d != 1):
             raise NotImplementedError("training path of FusedConv2d: kernel 1|3, dilation 1|2|4|8, stride 2 only without dilation")
         sc = sh = None
@@ -683,7 +690,7 @@ class Conv2dUnitFn(torch.autograd.Function):
         dw = dx = dbias = None
         if ctx.needs_input_grad[1]:
             if k == 5:     # 5x5 stride 2 = 3x3 stride 1 on the space-to-depth input (GC-Net's first layer)
-                dw = _k3_as_k5s2_grad(ops.conv2d_wgrad(_space_to_depth(x).contiguous(), dc, 3, 1), x.shape[1])
+                dw = _k3_as_k5s2_grad(ops.conv2d_wgrad(_space_to_depth(_even(x)).contiguous(), dc, 3, 1), x.shape[1])
             elif s == 1:
                 dw = ops.conv2d_wgrad(x, dc, k, d)
             elif k == 3:   # stride 2: the 3-D stride-2 weight gradient at depth 1, middle plane of its taps
@@ -692,7 +699,7 @@ class Conv2dUnitFn(torch.autograd.Function):
                 dw = ops.conv2d_wgrad(x[:, :, ::2, ::2].contiguous(), dc, 1, 1)
         if ctx.needs_input_grad[0]:
             if k == 5:
-                dx = _depth_to_space(ops.conv2d_dgrad(dc, _k5s2_as_k3(w))).contiguous()
+                dx = _depth_to_space(ops.conv2d_dgrad(dc, _k5s2_as_k3(w)))[:, :, :x.shape[2], :x.shape[3]].contiguous()
             elif s == 1:
                 dx = ops.conv2d_dgrad(dc, w, d, residual=dx_acc, packs=_phase_pack(unit, w, False))
                 dx_acc = None
@@ -745,6 +752,13 @@ class BareConv1x1Fn(torch.autograd.Function):
                 ops.conv2d_wgrad(x, dy, 1, 1) if ctx.needs_input_grad[1] else None)
 
 
+def _even(x):
+    """x with a zero row / column appended to an odd height / width.  A 5x5 stride-2 layer (padding 2) reads that row or column as
+    padding anyway, so it has the same outputs on the even-sized input; its data gradient there is sliced off again."""
+    H, W = x.shape[2], x.shape[3]
+    return torch.nn.functional.pad(x, (0, W % 2, 0, H % 2)) if H % 2 or W % 2 else x
+
+
 def _space_to_depth(x):
     """[B, C, H, W] (even H, W) -> [B, 4C, H/2, W/2], channel order (c, row parity, column parity)."""
     B, C, H, W = x.shape
@@ -781,8 +795,6 @@ class BareConv2dFn(torch.autograd.Function):
         w = weight.detach().contiguous()
         Co, k = w.shape[0], w.shape[2]
         stride = 2 if k == 5 else 1
-        if k == 5 and (x.shape[2] % 2 or x.shape[3] % 2):
-            raise NotImplementedError("training path of the 5x5 stride-2 layers: even input sizes")
         b = bias.detach().contiguous() if bias is not None else None
         raw = ops.conv2d(x, ops.pack_conv2d_weights(w), Co, k, stride, 1, None, b, None, False)
         one, zero = _const(1.0, Co, x.device), _const(0.0, Co, x.device)
@@ -811,9 +823,9 @@ class BareConv2dFn(torch.autograd.Function):
         if k == 5:
             w3 = _k5s2_as_k3(w)
             if ctx.needs_input_grad[1]:
-                dw = _k3_as_k5s2_grad(ops.conv2d_wgrad(_space_to_depth(x).contiguous(), dc, 3, 1), Ci)
+                dw = _k3_as_k5s2_grad(ops.conv2d_wgrad(_space_to_depth(_even(x)).contiguous(), dc, 3, 1), Ci)
             if ctx.needs_input_grad[0]:
-                dx = _depth_to_space(ops.conv2d_dgrad(dc, w3)).contiguous()
+                dx = _depth_to_space(ops.conv2d_dgrad(dc, w3))[:, :, :x.shape[2], :x.shape[3]].contiguous()
         else:
             if ctx.needs_input_grad[1]:
                 dw = ops.conv2d_wgrad(x, dc, k, 1)
@@ -881,8 +893,12 @@ def wants_grad(module, *tensors):
     parameters (``model.train(); model.backbone.eval()`` freezes the backbone's BatchNorm statistics, not its weights: with
     the reference's plain nn modules those weights still get gradients, and so they do here; each BatchNorm follows its own
     ``training`` flag).  Under torch.no_grad() -- how the reference's tools run evaluation, and what
-    GeneralizedStereoModel's eval branch enters itself -- an eval-mode module always stays on the fused kernels."""
+    GeneralizedStereoModel's eval branch enters itself -- an eval-mode module stays on the fused kernels, unless (c) its
+    BatchNorm keeps no running buffers: that normalises with batch statistics in every mode, which no folded scale / shift
+    can express."""
     if module.training:
+        return True
+    if getattr(module, "has_bn", False) and _batch_stats(module[1]):
         return True
     if not torch.is_grad_enabled():
         return False

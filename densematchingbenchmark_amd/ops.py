@@ -7,6 +7,7 @@ product path has no fallback.
 import ctypes
 
 import torch
+from torch.optim.optimizer import register_optimizer_step_post_hook
 
 from . import _lib
 from ._lib import check, dev_ptr, host_floats, host_ints, stream_ptr
@@ -401,8 +402,9 @@ def view_streams():
 # Folded / packed parameter caches of the modules are keyed by (pointer, ``_version``) of their parameters -- and by this epoch.
 # Most in-place updates move ``_version`` (optimizer.step() of the for-loop / multi-tensor optimizers, load_state_dict, copy_), but
 # torch's FUSED optimizers (``Adam(fused=True)``) do not.  Every train() <-> eval() switch of a fused unit advances the epoch, so
-# an eval-mode forward after training re-folds whatever the versions say; code that rewrites parameters of an eval-mode model
-# behind torch's back calls ``bump_param_epoch()`` itself.
+# an eval-mode forward after training re-folds whatever the versions say.  Every optimizer step advances it too (a global step
+# hook, below): a module that stays in eval() while a fused optimizer updates its weights (frozen-BatchNorm fine-tuning) must not
+# be served packs from before the step.  Code that rewrites parameters behind torch's back calls ``bump_param_epoch()`` itself.
 _param_epoch = [0]
 
 
@@ -412,6 +414,9 @@ def param_epoch():
 
 def bump_param_epoch():
     _param_epoch[0] += 1
+
+
+register_optimizer_step_post_hook(lambda optimizer, args, kwargs: bump_param_epoch())
 
 
 def warm_packed_parameters(module):
@@ -823,6 +828,9 @@ def conv3d_k3_dgrad(dc, w, stride=1, in_size=None, residual=None, wpack=None):
     ``wpack``: the data gradient's packed weights when the caller already holds them (unit_pack_jobs)."""
     Co, Ci = w.shape[0], w.shape[1]
     if stride == 1:
+        if Ci not in _CONV_OUT_CHANNELS:
+            return _conv3d_k3_any_co(dc, Ci, 1, residual, lambda c0, n, npad: pack_conv3d_dgrad_weights(
+                torch.nn.functional.pad(w[:, c0:c0 + n], (0, 0, 0, 0, 0, 0, 0, npad - n))))
         return conv3d_k3(dc, wpack if wpack is not None else pack_conv3d_dgrad_weights(w), Ci, residual=residual)
     if stride == 2:
         # the adjoint of a stride-2 convolution is the transposed convolution with the same weight tensor; the transposed kernel
@@ -852,7 +860,30 @@ def conv3d_k3_dgrad(dc, w, stride=1, in_size=None, residual=None, wpack=None):
 def deconv3d_k3s2_dgrad(dy, w, residual=None, wpack=None):
     """Gradient of nn.ConvTranspose3d(k=3, s=2, p=1, output_padding=1) w.r.t. its input; w is [Ci, Co, 3, 3, 3].  ``residual`` and
     ``wpack`` as in conv3d_k3_dgrad."""
-    return conv3d_k3(dy, wpack if wpack is not None else pack_conv3d_weights(w), w.shape[0], residual=residual, stride=2)
+    Ci = w.shape[0]
+    if Ci not in _CONV_OUT_CHANNELS:
+        return _conv3d_k3_any_co(dy, Ci, 2, residual, lambda c0, n, npad: pack_conv3d_weights(
+            torch.nn.functional.pad(w[c0:c0 + n], (0, 0, 0, 0, 0, 0, 0, 0, 0, npad - n))))
+    return conv3d_k3(dy, wpack if wpack is not None else pack_conv3d_weights(w), Ci, residual=residual, stride=2)
+
+
+# Output channel counts dmb_conv3d_k3_f32 takes (stride 1 and 2).  A data gradient is a forward launch whose output channels are the
+# layer's INPUT channels, which may be any count: those run as launches of 128 / 64 / 32 channels, the last on zero-padded weights.
+_CONV_OUT_CHANNELS = (32, 64, 128)
+
+
+def _conv3d_k3_any_co(x, Co, stride, residual, pack_rows):
+    """conv3d_k3 with ``Co`` output channels of any count.  ``pack_rows(c0, n, npad)`` packs the convolution weights of output channels
+    c0 .. c0 + n - 1, zero-padded to npad channels.  ``residual`` is added after the slicing, outside the kernel."""
+    parts, c0 = [], 0
+    while c0 < Co:
+        n = next((m for m in (128, 64, 32) if m <= Co - c0), Co - c0)
+        npad = max(n, 32)
+        y = conv3d_k3(x, pack_rows(c0, n, npad), npad, stride=stride)
+        parts.append(y if n == npad else y[:, :n])
+        c0 += n
+    y = torch.cat(parts, 1) if len(parts) > 1 else parts[0].contiguous()
+    return y + residual if residual is not None else y
 
 
 def conv3d_k3_wgrad(x, dc):
@@ -922,16 +953,21 @@ def conv2d_k3_wgrad(x, dc):
     return conv2d_wgrad(x, dc, 3, 1)
 
 
-def conv2d_dgrad_packs(w):
+def conv2d_dgrad_packs(w, dilation=1):
     """Packed weights of the data-gradient convolution of a stride-1 nn.Conv2d with weight [Co, Ci, k, k]: the layer's taps mirrored,
-    channel roles exchanged, in chunks of at most 128 output (= the layer's input) channels: [(c0, n, pack), ...]."""
+    channel roles exchanged, in chunks of output (= the layer's input) channels that dmb_conv2d_f32 launches: at most 128, never
+    65 .. 96 (three 32-channel tiles), at most 32 with dilation 4 | 8: [(c0, n, pack), ...]."""
     w = _f32c(w, "weight")
     Ci = w.shape[1]
     wt = w.detach().transpose(0, 1).flip(2, 3).contiguous()           # [Ci, Co, k, k]: a convolution Co -> Ci
-    out = []
-    for c0 in range(0, Ci, 128):
-        n = min(128, Ci - c0)
+    cap = 32 if dilation > 2 else 128
+    out, c0 = [], 0
+    while c0 < Ci:
+        n = min(cap, Ci - c0)
+        if 64 < n <= 96:
+            n = 64
         out.append((c0, n, pack_conv2d_weights(wt[c0:c0 + n].contiguous() if n != Ci else wt)))
+        c0 += n
     return out
 
 
@@ -946,7 +982,7 @@ def conv2d_dgrad(dc, w, dilation=1, residual=None, packs=None):
     dx = torch.empty((B, Ci, H, W), dtype=torch.float32, device=dc.device)
     if residual is not None:
         residual = _f32c(residual, "residual")
-    for c0, n, pack in (packs if packs is not None else conv2d_dgrad_packs(w)):
+    for c0, n, pack in (packs if packs is not None else conv2d_dgrad_packs(w, dilation)):
         conv2d(dc, pack, n, k, dilation=dilation, residual=residual, out=dx, out_ch_offset=c0, res_ch_offset=c0)
     return dx
 
