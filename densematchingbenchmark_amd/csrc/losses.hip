@@ -48,18 +48,20 @@ struct Target {
     float tsum = 0.f, es = 0.f;
     for (int d = 0; d < D; ++d) {
       const float ad = fabsf(dv.v[d] - g);
-      const float ex = __expf(-ad * inv_v - tmax);
+      const float ex = expf(-ad * inv_v - tmax);
       tsum += ex;
       if (want_e) es = fmaf(ex, ad, es);
     }
     inv_tsum = 1.f / tsum;
     e = es * inv_tsum * inv_v2;
   }
-  __device__ float p(float s) const { return __expf(-fabsf(s - g) * inv_v - tmax) * inv_tsum; }   // plain softmax term
+  __device__ float p(float s) const { return expf(-fabsf(s - g) * inv_v - tmax) * inv_tsum; }   // plain softmax term
 };
 
+// The focal-loss passes use the full-precision expf / logf: the fast __expf / __logf approximations lose ~|argument| ulps, and
+// their arguments here reach -|s - g| / v (tens) and fc * log(1 - P) -- several times the error of the reference's FP32 CPU run.
 // a(P) = P * (1 - P)^(-fc); pw = (1 - P)^(-fc) is returned for the derivative a'(P) = pw + fc * P * pw / (1 - P).
-__device__ __forceinline__ float focal_pow(float P, float fc) { return fc == 0.f ? 1.f : __expf(-fc * __logf(1.f - P)); }
+__device__ __forceinline__ float focal_pow(float P, float fc) { return fc == 0.f ? 1.f : expf(-fc * logf(1.f - P)); }
 
 // Forward: one thread per pixel.  stats[pixel] = (logsumexp_d cost, sum_d a_d) for the backward pass.
 // partial[block] = (sum of -sum_d a_d * log q_d * m1, number of valid pixels).
@@ -82,10 +84,10 @@ __global__ __launch_bounds__(LOSS_BLOCK) void focal_fwd_kernel(const float* __re
     for (int d = 0; d < D; ++d) {
       const float c = cp[(long long)d * HW];
       if (c > m) {
-        se *= (m == -INFINITY) ? 0.0 : (double)__expf(m - c);
+        se *= (m == -INFINITY) ? 0.0 : (double)expf(m - c);
         m = c;
       }
-      se += (double)__expf(c - m);
+      se += (double)expf(c - m);
       const float P = tg.p(dv.v[d]) * tg.m2 + eps;
       const float a = P * focal_pow(P, fc);
       sac = fma((double)a, (double)c, sac);
@@ -147,7 +149,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void focal_bwd_kernel(const float* __re
     const float pd = tg.p(dv.v[d]);
     const float P = pd * tg.m2 + eps;
     const float pw = focal_pow(P, fc);
-    __builtin_nontemporal_store(k * (st.y * __expf(c - st.x) - P * pw), gp + (long long)d * HW);   // streaming gradient
+    __builtin_nontemporal_store(k * (st.y * expf(c - st.x) - P * pw), gp + (long long)d * HW);   // streaming gradient
     if (grad_var) {
       const float da = fc == 0.f ? 1.f : pw + fc * P * pw / (1.f - P);
       const float dt = fabsf(dv.v[d] - tg.g) * tg.inv_v2;

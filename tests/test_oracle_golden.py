@@ -355,6 +355,40 @@ def test_losses_vs_reference():
     assert abs(float(l.detach()) - g["l1_loss"][0]) <= 1e-6 and maxdiff(est.grad, g["l1_grad"]) <= 1e-8
 
 
+def test_head_sweep_loss_yardstick_vs_reference():
+    """The loss yardstick of tests/test_head_grads_gpu.py (tests/_head_ref.py: level scaling, pooling, both masks, the shared FP32
+    inputs) run in FP32 on the inputs of losses.npz against the reference's values and autograd gradients: a wrong restatement
+    there could otherwise hide a wrong kernel.  The ground truth goes in at twice the level's width as well (avg and max pooled):
+    the restatement's level path must give what the reference's own functions give on the pooled map."""
+    from tests import _head_ref as HR
+    g = golden("losses.npz")
+    gt = torch.from_numpy(g["gt"])
+    for tag, coef, var in (("a", 0.0, 1.2), ("b", 5.0, torch.from_numpy(g["focal_b_var"]).requires_grad_(True))):
+        cost = (rand((2, 48, 12, 20), 512) * 3.0).requires_grad_(True)
+        loss = 0.7 * HR.focal_level(cost, var, HR.focal_prep(gt, cost.shape, 48, 0, 1), coef)
+        loss.backward()
+        assert abs(float(loss.detach()) - g["focal_%s_loss" % tag][0]) <= 1e-5 * abs(g["focal_%s_loss" % tag][0])
+        assert maxdiff(cost.grad, g["focal_%s_gcost" % tag]) <= 1e-6 * np.abs(g["focal_%s_gcost" % tag]).max() + 1e-9
+        if tag == "b":
+            assert maxdiff(var.grad, g["focal_b_gvar"]) <= 1e-5 * np.abs(g["focal_b_gvar"]).max()
+    conf = (rand((2, 1, 12, 20), 513) * 2.0).requires_grad_(True)
+    l = HR.nll_level(conf, *HR.map_prep(gt, (12, 20), 48))
+    l.backward()
+    assert abs(float(l.detach()) - g["conf_loss"][0]) <= 1e-6 and maxdiff(conf.grad, g["conf_grad"]) <= 1e-8
+    est = (gt + rand((2, 1, 12, 20), 514) * 2.0).detach().requires_grad_(True)
+    l = HR.smooth_l1_level(est, *HR.map_prep(gt, (12, 20), 48))
+    l.backward()
+    assert abs(float(l.detach()) - g["l1_loss"][0]) <= 1e-6 and maxdiff(est.grad, g["l1_grad"]) <= 1e-8
+    # the level path: gt at twice the width, scaled by 2 (exact) and pooled, is the level's map with a halved bound
+    gt2 = gt.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3) * 2.0
+    for sparse in (False, True):
+        p1, p2 = HR.focal_prep(gt, (2, 48, 12, 20), 48), HR.focal_prep(gt2, (2, 48, 12, 20), 96, sparse=sparse)
+        assert torch.equal(p1["g"], p2["g"]) and torch.equal(p1["m1"], p2["m1"]) and torch.equal(p1["samples"], p2["samples"])
+        assert p2["samples"].numel() == 48 and HR.level_gt(gt2, (12, 20), sparse)[1] == 2.0
+        sg, mask = HR.map_prep(gt2, (12, 20), 96, sparse=sparse)
+        assert torch.equal(sg, gt) and torch.equal(mask, HR.map_prep(gt, (12, 20), 48)[1])
+
+
 def _fingerprint(t):
     f = t.detach().double().reshape(-1)
     step = max(1, f.numel() // 16)
