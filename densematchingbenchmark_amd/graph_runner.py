@@ -15,6 +15,8 @@ runner.  ``auto_threshold``: ``wants_graph(batch)`` says whether a batch is smal
 callers that default to graphs -- apis.inference_stereo, bench.py's latency legs -- ask it)."""
 import torch
 
+from .param_state import module_stamp
+
 # Below this many input elements per call (both views together) the host launch path is a measurable share of the step:
 # two 3 x 544 x 960 images at batch 1 = 3.1 M elements -> graph; batch 4 of them = 12.5 M -> eager (measured equal there:
 # 26.91 against 26.96 ms, profiles/r04 graph_replay_probe).  Feature inputs (32 channels at quarter resolution) count the same way.
@@ -55,27 +57,20 @@ class GraphedForward:
     def __init__(self, model, warmup=2, max_graphs=4, track_parameters=True):
         """``max_graphs``: graphs held at once (one per input signature, least recently used evicted).  Each pins a private
         memory pool with every intermediate of a forward -- for a 544x960 pair the three full-resolution cost volumes alone are
-        1.2 GB -- until it is evicted or ``reset()`` is called.  ``track_parameters``: compare every parameter's / buffer's (pointer, version) before each replay (~0.15 ms of host
-        time for PSMNet's 517 tensors) and re-capture after a change; False = the caller promises frozen weights (or calls
-        ``reset()`` after changing them)."""
+        1.2 GB -- until it is evicted or ``reset()`` is called.  Captured graphs hold the PACKED weights of the moment of capture.
+        ``track_parameters``: compare ``param_state.module_stamp(model)`` before each replay (~0.15 ms of host time for PSMNet's
+        517 tensors) and re-capture after a change; False = the caller promises frozen weights (or calls ``reset()`` after
+        changing them)."""
         self.model = model
         self.warmup = int(warmup)
         self.max_graphs = int(max_graphs)
         self.track_parameters = bool(track_parameters)
-        self._tensors = None
         self._graphs = {}      # signature -> (graph, static inputs {path: tensor}, outputs)
         self._order = []
-        self._params_key = None
+        self._stamp = None
 
     def _signature(self, flat):
         return tuple((p, tuple(t.shape), t.dtype, t.device) for p, t in flat)
-
-    def _parameters_key(self):
-        """Captured graphs hold the PACKED weights of the moment of capture: any in-place change of a parameter or buffer
-        (load_state_dict, an optimiser step) invalidates them."""
-        if self._tensors is None:      # the Parameter / buffer OBJECTS persist across .to() and load_state_dict(); walking the module
-            self._tensors = list(self.model.parameters()) + list(self.model.buffers())     # tree costs 1.6 ms, this list 0.15 ms
-        return tuple((t.data_ptr(), t._version) for t in self._tensors)
 
     def reset(self):
         self._graphs.clear()
@@ -103,10 +98,10 @@ class GraphedForward:
         if not flat or not all(t.is_cuda for _, t in flat):
             return self.model(batch)      # (raises the library's own error for CPU tensors)
         if self.track_parameters:
-            pk = self._parameters_key()
-            if pk != self._params_key:
+            stamp = module_stamp(self.model)
+            if stamp != self._stamp:
                 self.reset()
-                self._params_key = pk
+                self._stamp = stamp
         sig = self._signature(flat)
         entry = self._graphs.get(sig)
         if entry is None:

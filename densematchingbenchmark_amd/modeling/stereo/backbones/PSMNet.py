@@ -6,7 +6,7 @@ layer4's last blocks and the four up-sampled branches write straight into their 
 import torch
 import torch.nn as nn
 
-from .... import ops
+from .... import ops, param_state
 from ..layers import train_fn
 from ..layers.basic_layers_2d import BasicBlock, conv_bn, conv_bn_relu
 
@@ -97,14 +97,9 @@ class _BareConv1x1(nn.Conv2d):
 
     def __init__(self, in_planes, out_planes):
         super().__init__(in_planes, out_planes, kernel_size=1, padding=0, stride=1, dilation=1, bias=False)
-        self._key, self._wp = None, None
 
     def _prepacked(self):
-        from ..layers.basic_layers import _versions
-        key = _versions(self.weight)
-        if key != self._key:
-            self._key, self._wp = key, ops.pack_conv2d_weights(self.weight.detach())
-        return self._wp
+        return param_state.cached(self, "_dmb_packed", (self.weight,), lambda: ops.pack_conv2d_weights(self.weight.detach()))
 
     def forward(self, x):
         if train_fn.wants_grad(self, x):

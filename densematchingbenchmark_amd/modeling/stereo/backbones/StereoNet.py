@@ -4,9 +4,8 @@ fused HIP launch; both views run as one batch."""
 import torch
 import torch.nn as nn
 
-from .... import ops
+from .... import ops, param_state
 from ..layers import train_fn
-from ..layers.basic_layers import _versions
 from ..layers.basic_layers_2d import BasicBlock
 
 
@@ -17,14 +16,10 @@ class _HipConv2d(nn.Conv2d):
         super().__init__(in_planes, out_planes, kernel_size=kernel_size, stride=stride, padding=padding, bias=True)
         if padding != kernel_size // 2:
             raise NotImplementedError("HIP conv2d: 'same' padding only")
-        self._key, self._cache = None, None
 
     def _prepacked(self):
-        key = _versions(self.weight, self.bias)
-        if key != self._key:
-            self._key = key
-            self._cache = (ops.pack_conv2d_weights(self.weight.detach()), self.bias.detach().float().contiguous())
-        return self._cache
+        return param_state.cached(self, "_dmb_packed", (self.weight, self.bias), lambda: (
+            ops.pack_conv2d_weights(self.weight.detach()), self.bias.detach().float().contiguous()))
 
     def forward(self, x):
         if train_fn.wants_grad(self, x):

@@ -2,9 +2,9 @@
 convolution / BatchNorm / weight-gradient kernels under autograd)."""
 import torch.nn as nn
 
-from .... import ops
+from .... import ops, param_state
 from ..layers import train_fn
-from ..layers.basic_layers import _versions, fold_batch_norm
+from ..layers.basic_layers import bn_parts, fold_batch_norm
 
 
 class ConfHead(nn.Module):
@@ -22,24 +22,21 @@ class ConfHead(nn.Module):
         first.append(nn.ReLU(inplace=True))
         self.conf_net = nn.Sequential(nn.Sequential(*first), nn.Conv2d(self.sec_in_planes, 1, 1, 1, 0, bias=False))
         self.batch_norm = batch_norm
-        self._key, self._cache = None, None
 
     def _prepacked(self):
         conv1 = self.conf_net[0][0]
         bn = self.conf_net[0][1] if self.batch_norm else None
         conv2 = self.conf_net[1]
-        parts = [conv1.weight, conv2.weight] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked] if bn else [])
-        key = _versions(*parts)
-        if key != self._key:
+
+        def make():
             w1 = conv1.weight.detach()
             scale, shift = fold_batch_norm(bn, None, self.sec_in_planes, w1.device)
             if scale is None:
                 import torch
                 scale = torch.ones(self.sec_in_planes, device=w1.device)
                 shift = torch.zeros(self.sec_in_planes, device=w1.device)
-            self._key = key
-            self._cache = (ops.pack_conf_head_weights(w1), scale, shift, conv2.weight.detach().reshape(-1).contiguous())
-        return self._cache
+            return ops.pack_conf_head_weights(w1), scale, shift, conv2.weight.detach().reshape(-1).contiguous()
+        return param_state.cached(self, "_dmb_packed", (conv1.weight, conv2.weight) + bn_parts(bn), make)
 
     def forward(self, cost):
         wp, scale, shift, w2 = self._prepacked()
@@ -47,11 +44,11 @@ class ConfHead(nn.Module):
             # ``cost`` is AcfNet's learned 4x up-sampling of a quarter-resolution volume (the aggregator left a note on the
             # tensor): head o up-sampling = 16 phase-wise 3x3 convolutions of that volume, a quarter of the multiplications
             src = ops.UpsampleSource.lookup(cost)
-            key = _versions(self.conf_net[0][0].weight, src.w8) + (self._key,)
-            if getattr(self, "_comp_key", None) != key:
-                self._comp_key = key
-                self._comp = ops.conf_head_k8s4_pack(self.conf_net[0][0].weight, src.w8, scale, shift)
-            return ops.conf_head_from_source(cost, self._comp, scale, shift, w2)
+            # (scale and shift are tensors of the fold above: a new fold is a new source of this pack)
+            w1 = self.conf_net[0][0].weight
+            comp = param_state.cached(self, "_dmb_packed_composite", (w1, src.w8, scale, shift),
+                                      lambda: ops.conf_head_k8s4_pack(w1, src.w8, scale, shift))
+            return ops.conf_head_from_source(cost, comp, scale, shift, w2)
         return ops.conf_head(cost, wp, scale, shift, w2)
 
     def logits(self, cost):

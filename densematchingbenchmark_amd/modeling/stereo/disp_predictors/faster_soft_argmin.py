@@ -2,7 +2,7 @@
 import torch
 import torch.nn as nn
 
-from .... import ops
+from .... import ops, param_state
 from ..layers import train_fn
 from .soft_argmin import _SoftArgminBase
 
@@ -19,14 +19,10 @@ class FasterSoftArgmin(_SoftArgminBase):
         self.disp_regression = nn.Conv3d(1, 1, (self.disp_sample_number, 1, 1), 1, 0, bias=False)
         self.disp_regression.weight.data = disp_sample.view(1, 1, -1, 1, 1).clone()
         self.disp_regression.weight.requires_grad = False
-        self._vals_key, self._vals = None, None
 
     def _sample_values(self):
         w = self.disp_regression.weight
-        key = (w.data_ptr(), w._version, str(w.device))
-        if key != self._vals_key:
-            self._vals_key, self._vals = key, w.detach().reshape(-1).cpu().tolist()
-        return self._vals
+        return param_state.cached(self, "_dmb_values", (w,), lambda: w.detach().reshape(-1).cpu().tolist())
 
     def forward(self, cost_volume, disp_sample=None):
         self._check(cost_volume)

@@ -7,9 +7,8 @@ dmb/modeling/stereo/disp_refinement/utils/edge_aware.py:8-70 (same module tree a
 import torch
 import torch.nn as nn
 
-from ..... import ops
+from ..... import ops, param_state
 from ...layers import train_fn
-from ...layers.basic_layers import _versions
 from ...layers.basic_layers_2d import BasicBlock, conv_bn_relu
 
 
@@ -18,18 +17,14 @@ class _ResidualHead(nn.Conv2d):
 
     def __init__(self, in_planes):
         super().__init__(in_planes, 1, kernel_size=3, stride=1, padding=1, bias=True)
-        self._key, self._cache = None, None
 
     def forward(self, x, skip, res_ch_offset=0):
         if train_fn.wants_grad(self, x, skip):
             if res_ch_offset or skip.shape[1] != 1:
                 raise ValueError("_ResidualHead training path: the skip is the 1-channel up-sampled disparity")
             return train_fn.BareConv2dFn.apply(x, self.weight, self.bias, skip, True)
-        key = _versions(self.weight, self.bias)
-        if key != self._key:
-            self._key = key
-            self._cache = (ops.pack_conv2d_weights(self.weight.detach()), self.bias.detach().float().contiguous())
-        wp, bias = self._cache
+        wp, bias = param_state.cached(self, "_dmb_packed", (self.weight, self.bias), lambda: (
+            ops.pack_conv2d_weights(self.weight.detach()), self.bias.detach().float().contiguous()))
         return ops.conv2d(x, wp, 1, 3, 1, 1, None, bias, skip, True, res_ch_offset=res_ch_offset)
 
 

@@ -10,11 +10,11 @@ gradient) the same units run as autograd Functions on the HIP kernels (train_fn.
 import torch
 import torch.nn as nn
 
-from .... import ops
+from .... import ops, param_state
 from . import train_fn
 
 __all__ = ["FusedConv3d", "HeadConv3d", "HeadDeconv3d", "conv3d_bn", "conv3d_bn_relu", "deconv3d_bn", "deconv3d_bn_relu",
-           "fold_batch_norm"]
+           "bn_parts", "fold_batch_norm"]
 
 
 def fold_batch_norm(bn, conv_bias, out_planes, device):
@@ -38,19 +38,18 @@ def fold_batch_norm(bn, conv_bias, out_planes, device):
     return scale.float().contiguous(), shift.float().contiguous()
 
 
-def _versions(*tensors):
-    """Cache key of folded / packed parameters.  BatchNorm's ``num_batches_tracked`` is part of every key that covers running
-    statistics: the training-mode kernel rewrites ``running_mean`` / ``running_var`` through raw device pointers (their
-    ``_version`` does not move), but every such forward bumps ``num_batches_tracked`` in place."""
-    return tuple((t.data_ptr(), t._version, t.device) for t in tensors if t is not None) + (ops.param_epoch(),)
+def bn_parts(bn):
+    """The tensors a folded BatchNorm is derived from (none without one).  ``num_batches_tracked`` is among them: the
+    training-mode kernel rewrites ``running_mean`` / ``running_var`` through raw device pointers (their ``_version`` does not
+    move), but every such forward bumps ``num_batches_tracked`` in place."""
+    return () if bn is None else (bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked)
 
 
 def epoch_on_mode_switch(module, mode):
-    """Called from train(mode) of the fused modules: a switch between training and evaluation advances ops' parameter epoch, which
-    is part of every cache key above -- in-place updates that leave ``_version`` alone (torch's fused optimizers) are then seen by
-    the first eval-mode forward after training."""
+    """Called from train(mode) of the fused modules: a switch between training and evaluation advances the parameter epoch
+    (param_state), so the first forward after it re-folds whatever the versions say."""
     if bool(mode) != module.training:
-        ops.bump_param_epoch()
+        param_state.bump_param_epoch()
 
 
 class FusedConv3d(nn.Sequential):
@@ -81,7 +80,6 @@ class FusedConv3d(nn.Sequential):
         super().__init__(*layers)
         self.in_planes, self.out_planes, self.stride = in_planes, out_planes, stride
         self.transposed, self.has_bn, self.has_relu = transposed, bool(batch_norm), bool(relu)
-        self._cache_key, self._cache = None, None
 
     def train(self, mode=True):
         epoch_on_mode_switch(self, mode)
@@ -94,16 +92,12 @@ class FusedConv3d(nn.Sequential):
     def _prepacked(self):
         conv = self[0]
         bn = self[1] if self.has_bn else None
-        parts = [conv.weight, conv.bias]
-        if bn is not None:
-            parts += [bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked]
-        key = _versions(*parts)
-        if key != self._cache_key:
+
+        def make():
             w = conv.weight.detach()
             wp = ops.pack_deconv3d_weights(w) if self.transposed else ops.pack_conv3d_weights(w)
-            scale, shift = fold_batch_norm(bn, conv.bias, self.out_planes, w.device)
-            self._cache_key, self._cache = key, (wp, scale, shift)
-        return self._cache
+            return (wp,) + fold_batch_norm(bn, conv.bias, self.out_planes, w.device)
+        return param_state.cached(self, "_dmb_packed", (conv.weight, conv.bias) + bn_parts(bn), make)
 
     def forward(self, x, residual=None, relu=None, skip=None):
         """``residual`` is added BEFORE the activation (hourglass.py:67-81), ``skip`` AFTER it (GC-Net,
@@ -114,12 +108,10 @@ class FusedConv3d(nn.Sequential):
             if (residual is None and skip is None and not self.transposed and self.stride == 1 and not self._batch_stats()
                     and x.shape[1] == self.in_planes and G % 2 == 0 and self.out_planes == 32
                     and ops.catconv_applicable(x.reference_fm, x.target_fm, x.disp_idx, self.out_planes)):
-                key = _versions(self[0].weight)
-                if getattr(self, "_gwc_key", None) != key:
+                def make():
                     w = self[0].weight.detach()
-                    self._gwc_key = key
-                    self._gwc = (ops.pack_conv3d_weights(w[:, :G].contiguous()), ops.catconv_pack(w[:, G:].contiguous(), "cat"))
-                wp_g, packs = self._gwc
+                    return ops.pack_conv3d_weights(w[:, :G].contiguous()), ops.catconv_pack(w[:, G:].contiguous(), "cat")
+                wp_g, packs = param_state.cached(self, "_dmb_packed_gwc", (self[0].weight,), make)
                 _, scale, shift = self._prepacked()
                 # convolution is linear in its input channels: relu(scale * (conv(gwc) + maps(cat)) + shift), the maps' part
                 # entering the 3-D kernel's epilogue as its residual operand, already scaled
@@ -152,16 +144,12 @@ class FusedConv3d(nn.Sequential):
         return ops.conv3d_k3(x, wp, self.out_planes, scale, shift, residual, self.stride, act)
 
     def _prepacked_cat(self, kind):
-        key = _versions(self[0].weight) + (kind,)
-        if getattr(self, "_cat_key", None) != key:
-            self._cat_key, self._cat = key, ops.catconv_pack(self[0].weight.detach(), kind)
-        return self._cat
+        w = self[0].weight
+        return param_state.cached(self, "_dmb_packed_" + kind, (w,), lambda: ops.catconv_pack(w.detach(), kind))
 
     def _prepacked_x6(self):
-        key = _versions(self[0].weight)
-        if getattr(self, "_x6_key", None) != key:
-            self._x6_key, self._x6 = key, ops.pack_conv3d_x6_weights(self[0].weight.detach())
-        return self._x6
+        w = self[0].weight
+        return param_state.cached(self, "_dmb_packed_x6", (w,), lambda: ops.pack_conv3d_x6_weights(w.detach()))
 
 
 class HeadConv3d(nn.Conv3d):
@@ -170,7 +158,6 @@ class HeadConv3d(nn.Conv3d):
 
     def __init__(self, in_planes, bias=False):
         super().__init__(in_planes, 1, kernel_size=3, stride=1, padding=1, bias=bias)
-        self._bias_key, self._bias_val = None, 0.0
 
     def train(self, mode=True):
         epoch_on_mode_switch(self, mode)
@@ -186,10 +173,8 @@ class HeadConv3d(nn.Conv3d):
     def bias_value(self):
         if self.bias is None:
             return 0.0
-        key = _versions(self.bias)
-        if key != self._bias_key:  # one device->host read per weight load, not per call
-            self._bias_key, self._bias_val = key, float(self.bias.detach().cpu()[0])
-        return self._bias_val
+        # one device->host read per weight load, not per call
+        return param_state.cached(self, "_dmb_bias", (self.bias,), lambda: float(self.bias.detach().cpu()[0]))
 
 
 class HeadDeconv3d(nn.ConvTranspose3d):
@@ -198,16 +183,12 @@ class HeadDeconv3d(nn.ConvTranspose3d):
 
     def __init__(self, in_planes, out_planes):
         super().__init__(in_planes, out_planes, kernel_size=3, stride=2, padding=1, output_padding=1)
-        self._key, self._cache = None, None
 
     def forward(self, x):
         if train_fn.wants_grad(self, x):
             return train_fn.HeadDeconvFn.apply(x, self.weight, self.bias)
-        key = _versions(self.weight, self.bias)
-        if key != self._key:
-            self._key = key
-            self._cache = (ops.pack_deconv3d_weights(self.weight.detach()), self.bias.detach().float().contiguous())
-        wp, bias = self._cache
+        wp, bias = param_state.cached(self, "_dmb_packed", (self.weight, self.bias), lambda: (
+            ops.pack_deconv3d_weights(self.weight.detach()), self.bias.detach().float().contiguous()))
         return ops.deconv3d_k3s2(x, wp, self.out_channels, None, bias, None, False)
 
 

@@ -5,9 +5,9 @@ same factory names, argument order and ``state_dict`` keys; torch.nn modules are
 import torch
 import torch.nn as nn
 
-from .... import ops
+from .... import ops, param_state
 from . import train_fn
-from .basic_layers import _versions, epoch_on_mode_switch, fold_batch_norm
+from .basic_layers import bn_parts, epoch_on_mode_switch, fold_batch_norm
 
 __all__ = ["FusedConv2d", "conv_bn", "conv_bn_relu", "BasicBlock"]
 
@@ -37,7 +37,6 @@ class FusedConv2d(nn.Sequential):
         self.in_planes, self.out_planes = in_planes, out_planes
         self.kernel_size, self.stride, self.dilation = kernel_size, stride, dilation
         self.has_bn, self.has_relu = bool(batch_norm), bool(relu)
-        self._cache_key, self._cache = None, None
 
     def train(self, mode=True):
         epoch_on_mode_switch(self, mode)
@@ -46,13 +45,11 @@ class FusedConv2d(nn.Sequential):
     def _prepacked(self):
         conv = self[0]
         bn = self[1] if self.has_bn else None
-        parts = [conv.weight, conv.bias] + ([bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked] if bn is not None else [])
-        key = _versions(*parts)
-        if key != self._cache_key:
+
+        def make():
             w = conv.weight.detach()
-            scale, shift = fold_batch_norm(bn, conv.bias, self.out_planes, w.device)
-            self._cache_key, self._cache = key, (ops.pack_conv2d_weights(w), scale, shift)
-        return self._cache
+            return (ops.pack_conv2d_weights(w),) + fold_batch_norm(bn, conv.bias, self.out_planes, w.device)
+        return param_state.cached(self, "_dmb_packed", (conv.weight, conv.bias) + bn_parts(bn), make)
 
     def forward(self, x, residual=None, relu=None, in_window=None, out=None, out_ch_offset=0, res_ch_offset=0):
         if train_fn.wants_grad(self, x, residual):

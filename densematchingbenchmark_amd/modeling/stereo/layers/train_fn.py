@@ -21,7 +21,7 @@ import weakref
 
 import torch
 
-from .... import ops
+from .... import ops, param_state
 
 _RELU = {0: False, 1: True, 2: "pre"}
 _CONST = {}
@@ -108,58 +108,40 @@ def _mask_mode(code, has_skip):
 
 class _PackGroup:
     """Packed weights of every 3-D unit that has taken the training path on one device: the forward AND the data-gradient pack of
-    all of them are re-made by ONE launch per forward pass (ops.run_pack_table) instead of one launch per unit and direction (52
-    launches of 4.8 us in a PSMNet step).  The pack buffers and the device table persist; units are held weakly.
+    all of them are re-made by ONE launch (ops.run_pack_table) instead of one launch per unit and direction (52 launches of 4.8 us
+    in a PSMNet step).  The pack buffers and the device table of pack jobs persist; units are held weakly.
 
-    When to re-pack.  A weight's ``_version`` moving is one trigger, but torch's FUSED optimizers (``Adam(fused=True)``) update
-    parameters without moving it -- so the group also counts passes: a unit asking for its packs a second time within one
-    generation means a new forward pass has begun (every unit runs once per pass), the generation advances and everything is
-    re-packed, whatever the versions say.  One 19 us launch per pass either way.  The parameter epoch, which every optimizer step
-    advances (ops.bump_param_epoch), is a third trigger: it also covers a unit that sat out the pass before the step."""
+    Re-packed, all units at once, when the asking unit's weight no longer matches its stamp (param_state): an in-place update, or
+    an optimizer step, which advances the epoch -- one launch per training step.  Code that writes parameters where ``_version``
+    cannot see it (``.data`` in-place writes, raw pointers) calls ``bump_param_epoch()``.  Before every launch, units that died
+    or whose weight moved leave the group and the table of raw pointers is rebuilt: a dead or moved job is never launched."""
 
     def __init__(self, device):
-        self.device, self.entries, self.table, self.njobs, self.gen = device, {}, None, 0, 0
+        self.device, self.entries, self.table, self.njobs = device, {}, None, 0
 
-    def packs(self, unit, w):
+    def packs(self, unit, weight):
         e = self.entries.get(id(unit))
-        if e is None or e["unit"]() is not unit or e["ptr"] != w.data_ptr() or e["shape"] != tuple(w.shape):
-            jobs = ops.unit_pack_jobs(w, unit.transposed, unit.stride)
-            e = {"unit": weakref.ref(unit), "ptr": w.data_ptr(), "shape": tuple(w.shape), "version": None, "seen": -1, "packed": -1,
-                 "epoch": None, "jobs": jobs,
-                 "bufs": [torch.empty((ops.packed_floats(co, ci),), dtype=torch.float32, device=w.device) for co, ci, _ in jobs]}
-            self.entries[id(unit)] = e
-            self.table = None
-        if e["seen"] == self.gen:
-            self.gen += 1                # second request within a generation: a new forward pass
-        e["seen"] = self.gen
-        if e["packed"] != self.gen or e["version"] != w._version or e["epoch"] != ops.param_epoch() or self.table is None:
-            self._repack(unit, w)
+        if e is None or e["unit"]() is not unit or not e["stamp"].holds((weight,)):
+            if e is None or e["unit"]() is not unit or not e["stamp"].placed((weight,)):
+                jobs = ops.unit_pack_jobs(weight, unit.transposed, unit.stride)
+                e = {"unit": weakref.ref(unit), "stamp": param_state.Stamp((weight,)), "jobs": jobs,
+                     "bufs": [torch.empty((ops.packed_floats(co, ci),), dtype=torch.float32, device=weight.device)
+                              for co, ci, _ in jobs]}
+                self.entries[id(unit)] = e
+                self.table = None
+            self._repack()
         return e["bufs"]
 
-    def _repack(self, unit, w):
-        if self.table is None:
-            jobs, keep = [], {}
-            for k, e in self.entries.items():
-                u = e["unit"]()
-                if u is None:
-                    continue
-                wt = w if u is unit else u[0].weight.detach()
-                if wt.data_ptr() != e["ptr"] or tuple(wt.shape) != e["shape"] or not wt.is_contiguous() or wt.device != self.device:
-                    continue            # replaced since (load_state_dict keeps pointers; .to() / re-assignment does not): re-registers itself
-                keep[k] = e
-                for (co, ci, mode), buf in zip(e["jobs"], e["bufs"]):
-                    jobs.append((wt, buf, co, ci, mode))
-            self.entries = keep
-            self.table, self.njobs = ops.make_pack_table(jobs, self.device), len(jobs)
+    def _repack(self):
+        weights = {k: u[0].weight for k, u in ((k, e["unit"]()) for k, e in self.entries.items()) if u is not None}
+        live = {k: e for k, e in self.entries.items() if k in weights and e["stamp"].placed((weights[k],))}
+        if self.table is None or len(live) != len(self.entries):
+            jobs = [(weights[k].detach(), buf, co, ci, mode)
+                    for k, e in live.items() for (co, ci, mode), buf in zip(e["jobs"], e["bufs"])]
+            self.entries, self.table, self.njobs = live, ops.make_pack_table(jobs, self.device), len(jobs)
         ops.run_pack_table(self.table, self.njobs)
-        dead = False
-        for e in self.entries.values():
-            u = e["unit"]()
-            e["packed"], e["epoch"] = self.gen, ops.param_epoch()
-            e["version"] = None if u is None else u[0].weight._version
-            dead = dead or u is None
-        if dead:
-            self.table = None           # a unit died: its job still ran (the buffers are ours), the next re-pack leaves it out
+        for k, e in self.entries.items():
+            e["stamp"] = param_state.Stamp((weights[k],))
 
 
 _pack_groups = {}
@@ -174,14 +156,15 @@ def set_pack_group(flag):
 
 def _unit_packs(unit, w):
     """(forward pack, data-gradient pack) of a unit's weight; the data-gradient pack may be None (made on demand)."""
-    if not _pack_group_enabled or torch.cuda.is_current_stream_capturing():
+    weight = unit[0].weight
+    if not _pack_group_enabled or torch.cuda.is_current_stream_capturing() or not weight.is_contiguous():
         fwd = ops.pack_deconv3d_weights(w) if unit.transposed else ops.pack_conv3d_weights(w)
         return fwd, None
     key = (w.device.type, w.device.index)
     g = _pack_groups.get(key)
     if g is None:
         g = _pack_groups[key] = _PackGroup(w.device)
-    return tuple(g.packs(unit, w))
+    return tuple(g.packs(unit, weight))
 
 
 def _conv_raw(unit, x, wpack, bias):
@@ -628,19 +611,17 @@ def _as3d_weight(w):
 # same modules one after the other (backbones/PSMNet.py:119-131), so every unit packed its forward weights twice per step and
 # built its data-gradient weights (a transpose, a flip, a copy, a pack) twice.  A pack now lives for a PHASE: the forward pack from
 # the first forward call until the unit's next backward call, the data-gradient packs from the first backward call until the next
-# forward call.  Parameters only change between a backward phase and the next forward phase (whatever the optimizer does to
-# ``_version``: see _PackGroup), so nothing stale survives; the version and the parameter epoch are part of the key for the
-# updates that do not follow a backward pass (load_state_dict).
+# forward call -- and, within its phase, while the weight matches its stamp (param_state: load_state_dict, an optimizer step).
 def _phase_pack(unit, w, forward):
-    key = (w.data_ptr(), tuple(w.shape), w._version, ops.param_epoch())
     mine, other = ("_dmb_pack_fwd", "_dmb_pack_bwd") if forward else ("_dmb_pack_bwd", "_dmb_pack_fwd")
-    d = unit.__dict__
-    d[other] = None
-    c = d.get(mine)
-    if c is None or c[0] != key or not _pack_group_enabled or torch.cuda.is_current_stream_capturing():
-        c = (key, ops.pack_conv2d_weights(w) if forward else ops.conv2d_dgrad_packs(w, unit.dilation))
-        d[mine] = c
-    return c[1]
+    unit.__dict__[other] = None
+
+    def make():
+        return ops.pack_conv2d_weights(w) if forward else ops.conv2d_dgrad_packs(w, unit.dilation)
+    if not _pack_group_enabled or torch.cuda.is_current_stream_capturing():
+        unit.__dict__[mine] = None
+        return make()
+    return param_state.cached(unit, mine, (unit[0].weight,), make)
 
 
 class Conv2dUnitFn(torch.autograd.Function):

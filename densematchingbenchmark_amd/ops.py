@@ -7,10 +7,10 @@ product path has no fallback.
 import ctypes
 
 import torch
-from torch.optim.optimizer import register_optimizer_step_post_hook
 
-from . import _lib
+from . import _lib, param_state
 from ._lib import check, dev_ptr, host_floats, host_ints, stream_ptr
+from .param_state import bump_param_epoch, param_epoch  # noqa: F401  (the names INTEGRATION.md points users at)
 
 
 def disp_index_list(max_disp, start_disp=0, dilation=1):
@@ -399,44 +399,19 @@ def view_streams():
     return _view_streams
 
 
-# Folded / packed parameter caches of the modules are keyed by (pointer, ``_version``) of their parameters -- and by this epoch.
-# Most in-place updates move ``_version`` (optimizer.step() of the for-loop / multi-tensor optimizers, load_state_dict, copy_), but
-# torch's FUSED optimizers (``Adam(fused=True)``) do not.  Every train() <-> eval() switch of a fused unit advances the epoch, so
-# an eval-mode forward after training re-folds whatever the versions say.  Every optimizer step advances it too (a global step
-# hook, below): a module that stays in eval() while a fused optimizer updates its weights (frozen-BatchNorm fine-tuning) must not
-# be served packs from before the step.  Code that rewrites parameters behind torch's back calls ``bump_param_epoch()`` itself.
-_param_epoch = [0]
-
-
-def param_epoch():
-    return _param_epoch[0]
-
-
-def bump_param_epoch():
-    _param_epoch[0] += 1
-
-
-register_optimizer_step_post_hook(lambda optimizer, args, kwargs: bump_param_epoch())
-
-
 def warm_packed_parameters(module):
     """Fill (on the CURRENT stream) every lazily packed / folded parameter cache below ``module``: each fused unit keeps its packed
-    weights and folded BatchNorm affine keyed by the parameters' versions (``_prepacked()``) and refills them inside its first
-    forward after a change -- pack kernels and torch ops on whatever stream that forward runs on.
-    Cheap when nothing changed: the walk over the module tree (1.6 ms for PSMNet's backbone) only happens when the (pointer, version)
-    key of the module's parameters and buffers differs from the one of the last warm-up (0.1 ms to compute)."""
-    tensors = module.__dict__.get("_dmb_warm_tensors")
-    if tensors is None:
-        tensors = list(module.parameters()) + list(module.buffers())     # the objects persist across .to() and load_state_dict()
-        module.__dict__["_dmb_warm_tensors"] = tensors
-    key = (module.training, _param_epoch[0]) + tuple((t.data_ptr(), t._version) for t in tensors)
-    if module.__dict__.get("_dmb_warm_key") == key:
+    weights and folded BatchNorm affine under the rule of param_state (``_prepacked()``) and refills them inside its first forward
+    after a change -- pack kernels and torch ops on whatever stream that forward runs on.  Cheap when nothing changed: the walk
+    over the module tree only happens when ``param_state.module_stamp(module)`` differs from the one of the last warm-up."""
+    stamp = param_state.module_stamp(module)
+    if module.__dict__.get("_dmb_warmed") == stamp:
         return
     for m in module.modules():
         pre = getattr(m, "_prepacked", None)
         if pre is not None:
             pre()
-    module.__dict__["_dmb_warm_key"] = key
+    module.__dict__["_dmb_warmed"] = stamp
 
 
 def two_view_forward(fn, left, right, module=None):

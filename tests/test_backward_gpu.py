@@ -1071,8 +1071,8 @@ def test_pack_group_repacks_every_unit_in_one_launch(dev):
 
 def test_fused_optimizer_updates_are_seen(dev):
     """torch's fused optimizers update parameters WITHOUT moving their ``_version`` (checked here), which every packed / folded
-    parameter cache of this package keys on.  The training path's pack group therefore re-packs once per forward pass whatever the
-    versions say, and a train() -> eval() switch advances ops' parameter epoch: (a) two Adam(fused=True) steps give the same losses
+    parameter cache of this package checks.  Every optimizer step therefore advances the parameter epoch (param_state's step
+    hook), as does a train() -> eval() switch, and the training path's pack group re-packs after it: (a) two Adam(fused=True) steps give the same losses
     with the pack group as with per-call packing, bit for bit; (b) the eval-mode forward after them equals a fresh model loaded
     with the trained state."""
     import os
@@ -1360,3 +1360,71 @@ def test_fused_optimizer_updates_are_seen_by_the_backbone(dev):
 
     on, off = run(True), run(False)
     assert on == off and on[0] != on[1] != on[2]
+
+
+def test_pack_table_never_launches_a_dead_unit(dev, monkeypatch):
+    """train_fn._PackGroup keeps one device table of raw weight pointers for the 3-D units of every model that trained on the
+    device.  After one of two models is deleted, the repack that the other model's next optimizer step makes due must rebuild
+    the table from the live units before launching it: every job of every launched table belongs to a live unit and points at
+    that unit's weight (checked by a wrapper BEFORE the launch, so nothing stale ever runs)."""
+    import gc
+    import os
+    import weakref
+    from densematchingbenchmark_amd import ops, synthetic
+    from densematchingbenchmark_amd.config import Config
+    from densematchingbenchmark_amd.modeling import build_model
+    from densematchingbenchmark_amd.modeling.stereo.layers.basic_layers import FusedConv3d
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cfg = Config.fromfile(os.path.join(root, "configs", "PSMNet", "scene_flow.py"))
+    md = 32
+    cfg.model.max_disp = md
+    cfg.model.cost_processor.cost_computation.max_disp = md // 4
+    cfg.model.cost_processor.cost_aggregator.max_disp = md
+    cfg.model.disp_predictor.max_disp = md
+    cfg.model.losses.l1_loss.max_disp = md
+    lf, rf = _rand((1, 32, 8, 24), 95).to(dev), _rand((1, 32, 8, 24), 96).to(dev)
+    gt = (torch.rand((1, 1, 32, 96), generator=torch.Generator().manual_seed(97)) * 30.0 + 1.0).to(dev)
+
+    def new_model(seed):
+        model = build_model(cfg, backbone=None).to(dev)
+        synthetic.init_params_(model, seed=seed)
+        return model.train(), torch.optim.SGD(model.parameters(), lr=1e-3)
+
+    def step(model, opt):
+        opt.zero_grad(set_to_none=True)
+        _, losses = model(dict(leftFeature=lf, rightFeature=rf, leftDisp=gt))
+        sum(losses.values()).backward()
+        opt.step()
+
+    a, opt_a = new_model(21)
+    b, opt_b = new_model(22)
+    step(a, opt_a)
+    step(b, opt_b)
+    dead = weakref.ref(a)
+    del a, opt_a
+    gc.collect()
+    assert dead() is None
+    live = {}
+    tables = {}
+    make, run = ops.make_pack_table, ops.run_pack_table
+
+    def make_spy(jobs, device):
+        table = make(jobs, device)
+        tables[id(table)] = (table, [w.data_ptr() for w, *_ in jobs])
+        return table
+
+    def run_spy(table, njobs):
+        ptrs = tables[id(table)][1] if id(table) in tables else None
+        assert ptrs is not None, "a table made before the deleted model died was launched"
+        assert len(ptrs) == njobs and all(p in live for p in ptrs), "a job of a dead or moved unit is about to launch"
+        run(table, njobs)
+        launched.append(njobs)
+
+    launched = []
+    live.update({m[0].weight.data_ptr(): m for m in b.modules() if isinstance(m, FusedConv3d)})
+    monkeypatch.setattr(ops, "make_pack_table", make_spy)
+    monkeypatch.setattr(ops, "run_pack_table", run_spy)
+    step(b, opt_b)                # the repack due after the optimizer step of the model that survived
+    torch.cuda.synchronize()
+    assert len(launched) == 1 and 0 < launched[0] <= 2 * len(live)      # b's packs, in one launch
+

@@ -226,3 +226,50 @@ def test_backbone_with_its_two_view_streams_captures(dev):
         with torch.no_grad():
             want = bb(l2, r2)
         assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), rep
+
+
+def test_graphed_forward_recaptures_after_a_fused_step_and_a_replaced_parameter(dev):
+    """GraphedForward replays graphs that hold the packs of the weights at capture.  A fused optimizer step (which leaves
+    ``_version`` alone) and a replaced Parameter object must both make the next call re-capture: its output equals a fresh eager
+    forward of the updated model, bit for bit."""
+    import torch.nn as nn
+    from densematchingbenchmark_amd import synthetic
+    from densematchingbenchmark_amd.config import Config
+    from densematchingbenchmark_amd.graph_runner import GraphedForward
+    from densematchingbenchmark_amd.modeling import build_model
+    from densematchingbenchmark_amd.modeling.stereo.layers.basic_layers import FusedConv3d
+    cfg = Config.fromfile(os.path.join(ROOT, "configs", "PSMNet", "scene_flow.py"))
+    md = 32
+    cfg.model.max_disp = md
+    cfg.model.cost_processor.cost_computation.max_disp = md // 4
+    cfg.model.cost_processor.cost_aggregator.max_disp = md
+    cfg.model.disp_predictor.max_disp = md
+    model = build_model(cfg, backbone=None).eval()
+    synthetic.init_params_(model, seed=5, classif_gain=10.0)
+    model = model.to(dev)
+    left, right = synthetic.feature_batch(0, 1, 1, 32, 8, 24, dev)
+    batch = dict(leftFeature=left, rightFeature=right)
+    gf = GraphedForward(model)
+
+    def check():
+        res = gf(batch)[0]
+        got = [t.clone() for t in list(res["disps"]) + list(res["costs"])]
+        with torch.no_grad():
+            res = model(batch)[0]
+        want = list(res["disps"]) + list(res["costs"])
+        assert len(got) == len(want) and all(torch.equal(a, b) for a, b in zip(got, want))
+        return got[-1]
+
+    d0 = check()
+    params = [p for p in model.parameters() if p.requires_grad]
+    for i, p in enumerate(params):
+        p.grad = torch.full_like(p, 1e-2 if i % 2 else -1e-2)
+    versions = [p._version for p in params]
+    torch.optim.Adam(params, lr=1e-4, fused=True).step()
+    assert [p._version for p in params] == versions      # the premise: a fused step leaves the versions alone
+    d1 = check()
+    assert not torch.equal(d0, d1)
+    unit = next(m for m in model.modules() if isinstance(m, FusedConv3d))
+    unit[0].weight = nn.Parameter(unit[0].weight.detach() * 0.5)
+    d2 = check()
+    assert not torch.equal(d1, d2)

@@ -602,3 +602,51 @@ def test_gradient_carry_scope_bookkeeping():
         t.join()
         assert seen == [None]
     assert train_fn._registry() is None and reg == {}
+
+
+def test_param_state_stamp_and_module_stamp():
+    """param_state, the one staleness rule of the packed / folded parameter caches: a cached value is re-made when a source
+    tensor was updated in place, when the parameter epoch advanced (an optimizer step, ``bump_param_epoch()``) and when a
+    Parameter object was replaced -- even by one on the same storage with the same version counter.  ``module_stamp`` (the
+    warm-up of two_view_forward, GraphedForward) changes after a Parameter is replaced, after ``load_state_dict(assign=True)``
+    and after a submodule swap, and not when nothing happened."""
+    import torch.nn as nn
+    from densematchingbenchmark_amd import param_state
+    m = nn.Conv2d(2, 3, 1)
+    made = []
+
+    def value():
+        return param_state.cached(m, "_test_value", (m.weight, m.bias, None), lambda: made.append(1) or len(made))
+
+    assert value() == 1 and value() == 1                     # unchanged: a hit
+    with torch.no_grad():
+        m.weight.add_(1.0)
+    assert value() == 2 and value() == 2                     # in-place update
+    param_state.bump_param_epoch()
+    assert value() == 3
+    assert ops.bump_param_epoch is param_state.bump_param_epoch and ops.param_epoch is param_state.param_epoch
+    epoch = ops.param_epoch()
+    m.weight.grad = torch.zeros_like(m.weight)
+    torch.optim.SGD([m.weight], lr=0.0).step()
+    assert ops.param_epoch() == epoch + 1 and value() == 4   # the optimizer step hook
+    old = m.weight
+    m.weight = nn.Parameter(old.detach())
+    assert m.weight.data_ptr() == old.data_ptr() and m.weight._version == old._version
+    assert value() == 5 and value() == 5                     # a replaced Parameter object
+    assert "_test_value" not in m.state_dict() and "_test_value" not in dict(m.named_parameters())
+
+    net = nn.Sequential(nn.Conv2d(2, 3, 1), nn.BatchNorm2d(3))
+    s0 = param_state.module_stamp(net)
+    nn.Conv2d(1, 1, 1)                                       # a registration elsewhere
+    assert param_state.module_stamp(net) == s0               # nothing happened to net
+    net[0].weight = nn.Parameter(net[0].weight.detach())     # same pointer, same version
+    s1 = param_state.module_stamp(net)
+    assert s1 != s0 and param_state.module_stamp(net) == s1
+    net.load_state_dict(net.state_dict(), assign=True)       # new Parameter objects on the same storages
+    s2 = param_state.module_stamp(net)
+    assert s2 != s1 and param_state.module_stamp(net) == s2
+    net[1] = nn.BatchNorm2d(3)
+    s3 = param_state.module_stamp(net)
+    assert s3 != s2 and param_state.module_stamp(net) == s3
+    net.load_state_dict({k: v.clone() for k, v in net.state_dict().items()})    # in place: the versions move
+    assert param_state.module_stamp(net) != s3

@@ -584,3 +584,49 @@ def test_backbone_views_on_two_streams_equal_one_batch(dev):
             finally:
                 ops.set_view_streams(True)
         assert torch.equal(fl, gl) and torch.equal(fr, gr) and s == (gl.sum() + gr.sum()).item()
+
+
+def test_two_view_warm_up_sees_a_replaced_parameter(dev, monkeypatch):
+    """ops.two_view_forward fills the packed-weight caches on the CALLER's stream before it forks the second view onto a side
+    stream.  After a backbone Parameter object is replaced, that warm-up must run again -- otherwise the new packs are made
+    inside one view's chain while the other view's chain reads them.  A spy on the replaced unit's ``_prepacked`` sees its first
+    call on the caller's stream before the fork, and the features equal those of a freshly built backbone with the same weights."""
+    import torch.nn as nn
+    from densematchingbenchmark_amd import ops, synthetic
+    from densematchingbenchmark_amd.modeling.stereo.backbones import PSMNetBackbone
+    from densematchingbenchmark_amd.modeling.stereo.layers.basic_layers_2d import FusedConv2d
+    bb = PSMNetBackbone(3, True).eval()
+    synthetic.init_params_(bb, seed=8, classif_gain=1.0)
+    bb = bb.to(dev)
+    l, r = rand((1, 3, 256, 512), 443).to(dev), rand((1, 3, 256, 512), 444).to(dev)
+    assert ops.view_streams()
+    with torch.no_grad():
+        bb(l, r)                                             # warm: the caches hold the initial weights
+    unit = [m for m in bb.modules() if isinstance(m, FusedConv2d)][-1]
+    unit[0].weight = nn.Parameter(unit[0].weight.detach() * 0.5)
+    events = []
+    prepacked, side_stream = unit._prepacked, ops.side_stream
+
+    def prepacked_spy():
+        events.append(("prepacked", torch.cuda.current_stream(dev)))
+        return prepacked()
+
+    def side_stream_spy(*args):
+        events.append(("fork", None))
+        return side_stream(*args)
+
+    monkeypatch.setattr(ops, "side_stream", side_stream_spy)
+    unit._prepacked = prepacked_spy
+    main = torch.cuda.current_stream(dev)
+    try:
+        with torch.no_grad():
+            fl, fr = bb(l, r)
+    finally:
+        del unit._prepacked
+    assert events and events[0] == ("prepacked", main), events[:3]
+    fresh = PSMNetBackbone(3, True).eval().to(dev)
+    fresh.load_state_dict(bb.state_dict())
+    with torch.no_grad():
+        gl, gr = fresh(l, r)
+    assert torch.equal(fl, gl) and torch.equal(fr, gr)
+
