@@ -114,6 +114,10 @@ SIGNATURES = {
     "dmb_stereo_pad_normalize_f32": (_c_int, [_P, _P] + [_c_int] * 11 + [_HF, _HF, _P]),
     "dmb_stereo_pad_normalize_u8": (_c_int, [_P, _P] + [_c_int] * 11 + [_HF, _HF, _P]),
     "dmb_map_loss_bwd_f32": (_c_int, [_P, _P, _P, _P, _c_float, _P, _c_ll, _c_float, _c_float, _c_int, _P]),
+    "dmb_preact_conv_f32": (_c_int, [_P, _P, _c_int] + [_P] * 9 + [_c_int] * 13 + [_P]),
+    "dmb_anynet_stage_samples_f32": (_c_int, [_P] * 4 + [_c_int] * 6 + [_c_float, _P]),
+    "dmb_add_f32": (_c_int, [_P, _P, _P, _c_ll, _P]),
+    "dmb_anynet_final_maps_f32": (_c_int, [_P] * 4 + [_HI, _HI, _P] + [_c_int] * 3 + [_P]),
 }
 
 

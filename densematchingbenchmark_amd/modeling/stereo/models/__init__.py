@@ -1,6 +1,7 @@
+from .AnyNet import AnyNet
 from .general_stereo_model import GeneralizedStereoModel
 
-_META_ARCHITECTURES = {"GeneralizedStereoModel": GeneralizedStereoModel}
+_META_ARCHITECTURES = {"GeneralizedStereoModel": GeneralizedStereoModel, "AnyNet": AnyNet}
 
 
 def build_stereo_model(cfg, backbone="auto"):

@@ -1823,4 +1823,118 @@ def spn_gaterecurrent2d_bwd(X, G1, G2, G3, H_fwd, grad_out, horizontal, reverse)
     return tuple(outs)
 
 
+# ---------------------------------------------------------------------------------------------- AnyNet (csrc/preact_conv.hip)
+PREACT_POOL, PREACT_RELU_IN, PREACT_RELU_OUT, PREACT_GATE = 0x1, 0x2, 0x4, 0x8   # include/dmb_hip.h: DMB_PREACT_*
+PREACT_MAX_CI, PREACT_MAX_CO = 64, 32
+
+
+def preact_conv(x, w, stride=1, pool=False, pre_scale=None, pre_shift=None, pre_relu=False, post_scale=None, post_shift=None,
+                relu=False, residual=None, gate=False, in_window=None, x2=None, out=None, out_ch_offset=0):
+    """3x3 (x [B, Cx, H, W], w [Co, Ci, 3, 3]) or 3x3x3 (x [B, Cx, D, H, W], w [Co, Ci, 3, 3, 3]) convolution, padding 1, in ONE
+    launch with the pre-activation prologue and the epilogue of dmb_preact_conv_f32.  ``in_window=(offset, Ci)`` reads channels
+    [offset, offset + Ci) of x; ``x2`` (same shape as x) is a second view appended to the batch; ``out`` (optional) is a
+    [B (+ B2), Ctot, (D,) Ho, Wo] tensor written at channel ``out_ch_offset``.  ``gate=True`` returns (G1, G2, G3)."""
+    lib = _lib.load()
+    x = _f32c(x, "x")
+    w = _f32c(w, "weight")
+    ndim = x.dim() - 2
+    if ndim not in (2, 3) or w.dim() != ndim + 2 or tuple(w.shape[2:]) != (3,) * ndim:
+        raise _lib.DmbLibraryError("preact_conv: x %s with weight %s" % (tuple(x.shape), tuple(w.shape)))
+    B, Cx = x.shape[:2]
+    D = x.shape[2] if ndim == 3 else 1
+    H, W = x.shape[-2:]
+    coff, Ci = in_window if in_window is not None else (0, Cx)
+    Co = w.shape[0]
+    if w.shape[1] != Ci or coff < 0 or coff + Ci > Cx:
+        raise _lib.DmbLibraryError("preact_conv: weight %s for input window (%d, %d) of %d channels" % (tuple(w.shape), coff, Ci, Cx))
+    if Ci > PREACT_MAX_CI or Co > PREACT_MAX_CO:
+        raise _lib.DmbLibraryError("preact_conv: at most %d input and %d output channels" % (PREACT_MAX_CI, PREACT_MAX_CO))
+    Bt = B
+    if x2 is not None:
+        x2 = _f32c(x2, "x2")
+        _same_shape(x, x2, "preact_conv views")
+        Bt = 2 * B
+    Hc, Wc = (H // 2, W // 2) if pool else (H, W)
+    Ho, Wo = (Hc - 1) // stride + 1, (Wc - 1) // stride + 1
+    inner = (D, Ho, Wo) if ndim == 3 else (Ho, Wo)
+    for t, n, c in ((pre_scale, "pre_scale", Ci), (pre_shift, "pre_shift", Ci), (post_scale, "post_scale", Co),
+                    (post_shift, "post_shift", Co)):
+        if t is not None and (t.numel() != c or not t.is_contiguous()):
+            raise _lib.DmbLibraryError("preact_conv: %s has %d elements for %d channels" % (n, t.numel(), c))
+    if residual is not None:
+        residual = _f32c(residual, "residual")
+        if tuple(residual.shape) != (Bt, Co) + inner:
+            raise _lib.DmbLibraryError("preact_conv: residual %s, expected %s" % (tuple(residual.shape), (Bt, Co) + inner))
+    flags = (PREACT_POOL if pool else 0) | (PREACT_RELU_IN if pre_relu else 0) | (PREACT_RELU_OUT if relu else 0)
+    ys = [None, None]
+    if gate:
+        if Co % 3 or out is not None:
+            raise _lib.DmbLibraryError("preact_conv: gate normalisation needs 3P output channels and its own outputs")
+        flags |= PREACT_GATE
+        out, *rest = [torch.empty((Bt, Co // 3) + inner, dtype=torch.float32, device=x.device) for _ in range(3)]
+        ys = [dev_ptr(t) for t in rest]
+        octot, out_ch_offset = Co // 3, 0
+    else:
+        if out is None:
+            out = torch.empty((Bt, Co) + inner, dtype=torch.float32, device=x.device)
+            out_ch_offset = 0
+        if (out.dim() != ndim + 2 or out.shape[0] != Bt or tuple(out.shape[2:]) != inner or out_ch_offset < 0
+                or out_ch_offset + Co > out.shape[1]):
+            raise _lib.DmbLibraryError("preact_conv: output tensor %s does not fit" % (tuple(out.shape),))
+        octot = out.shape[1]
+    check(lib.dmb_preact_conv_f32(dev_ptr(x), dev_ptr(x2, allow_none=True), B, dev_ptr(w),
+                                  dev_ptr(pre_scale, allow_none=True), dev_ptr(pre_shift, allow_none=True),
+                                  dev_ptr(post_scale, allow_none=True), dev_ptr(post_shift, allow_none=True),
+                                  dev_ptr(residual, allow_none=True),
+                                  dev_ptr(out), ys[0], ys[1], Bt, Ci, Co, D, H, W, ndim, int(stride),
+                                  flags, Cx, coff, octot, out_ch_offset, stream_ptr(x.device)), "dmb_preact_conv_f32")
+    return (out, *rest) if gate else out
+
+
+def anynet_stage_samples(low, size, scale, lin=None):
+    """models/AnyNet.py:84 / cost_processors/AnyNet.py:64-70: up = F.interpolate(low * scale, size, bilinear,
+    align_corners=False) [B, 1, H, W] and, with ``lin`` (device [D]), samples = lin.view(1, D, 1, 1) + up [B, D, H, W]."""
+    lib = _lib.load()
+    low = _f32c(low, "low")
+    if low.dim() != 4 or low.shape[1] != 1:
+        raise _lib.DmbLibraryError("anynet_stage_samples: low must be [B, 1, h, w], got %s" % (tuple(low.shape),))
+    B, _, h, w = low.shape
+    H, W = size
+    up = torch.empty((B, 1, H, W), dtype=torch.float32, device=low.device)
+    samples, D = None, 0
+    if lin is not None:
+        lin = _f32c(lin, "lin")
+        D = lin.numel()
+        samples = torch.empty((B, D, H, W), dtype=torch.float32, device=low.device)
+    check(lib.dmb_anynet_stage_samples_f32(dev_ptr(low), dev_ptr(lin, allow_none=True), dev_ptr(up),
+                                           dev_ptr(samples, allow_none=True), B, h, w, H, W, D, float(scale),
+                                           stream_ptr(low.device)), "dmb_anynet_stage_samples_f32")
+    return up, samples
+
+
+def add(a, b):
+    lib = _lib.load()
+    a, b = _f32c(a, "a"), _f32c(b, "b")
+    _same_shape(a, b, "add")
+    c = torch.empty_like(a)
+    check(lib.dmb_add_f32(dev_ptr(a), dev_ptr(b), dev_ptr(c), a.numel(), stream_ptr(a.device)), "dmb_add_f32")
+    return c
+
+
+def anynet_final_maps(disps, size):
+    """models/AnyNet.py:117-118,137-140: the 4 maps ``disps`` [B, 1, h_k, w_k] brought to ``size`` as
+    F.interpolate((d * W) / w) and the 3 differences of neighbours, as 7 contiguous [B, 1, H, W] views of one tensor."""
+    lib = _lib.load()
+    ds = [_f32c(d, "disp") for d in disps]
+    if len(ds) != 4 or any(d.dim() != 4 or d.shape[1] != 1 or d.shape[0] != ds[0].shape[0] for d in ds):
+        raise _lib.DmbLibraryError("anynet_final_maps: 4 maps [B, 1, h, w] expected")
+    B = ds[0].shape[0]
+    H, W = size
+    out = torch.empty((7, B, 1, H, W), dtype=torch.float32, device=ds[0].device)
+    check(lib.dmb_anynet_final_maps_f32(*[dev_ptr(d) for d in ds], host_ints([d.shape[2] for d in ds]),
+                                        host_ints([d.shape[3] for d in ds]), dev_ptr(out), B, H, W, stream_ptr(out.device)),
+          "dmb_anynet_final_maps_f32")
+    return list(out.unbind(0))
+
+
 from .spn import GateRecurrent2dnoind  # noqa: E402,F401  (``dmb.ops.GateRecurrent2dnoind``: dmb/ops/__init__.py:1)

@@ -611,6 +611,51 @@ int dmb_conv3d_k3_x6_f32(const float* x, const void* wpack, const float* scale, 
                          const float* residual, float* y, int B, int Ci, int Co, int D, int H, int W, int relu,
                          void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * AnyNet (models/AnyNet.py): pre-activation small-channel convolutions and the stage arithmetic
+ * ---------------------------------------------------------------------------------------- */
+
+#define DMB_PREACT_MAX_CI 64
+#define DMB_PREACT_MAX_CO 32
+#define DMB_PREACT_POOL 0x1     /* 2x2/2 max-pool of the input first (2-D; odd sizes floor, nn.MaxPool2d(2, 2)) */
+#define DMB_PREACT_RELU_IN 0x2  /* ReLU on the (pooled, scaled) input: bn_relu_conv's ReLU */
+#define DMB_PREACT_RELU_OUT 0x4 /* ReLU after the epilogue affine: conv_bn_relu's ReLU */
+#define DMB_PREACT_GATE 0x8     /* gate normalisation of a 3P-channel output (disp_refinement/AnyNet.py:75-78) */
+
+/* Direct 3x3 (ndim 2) / 3x3x3 (ndim 3) convolution, padding 1, dilation 1, stride 1 or 2 (2-D only), on 1 .. 64 input and
+ * 1 .. 32 output channels: bn_relu_conv / bn_relu_conv3d (layers/basic_layers.py:122-138,180-197), conv_bn_relu
+ * (:102-119) and plain nn.Conv2d.  w: the nn weight [Co, Ci, (3,) 3, 3] as it is.
+ *   prologue, per staged input element and only inside the image (padding stays 0): [max-pool] -> [x * pre_scale[c] +
+ *     pre_shift[c]] (both or neither: the folded eval-mode BatchNorm) -> [ReLU (DMB_PREACT_RELU_IN)];
+ *   each output: ONE ascending (ci, kz, ky, kx) fmaf chain from 0 -- independent of the launch size, so batch item i equals the
+ *     same item run alone bit for bit;
+ *   epilogue: [acc * post_scale[co] + post_shift[co] | acc + post_shift[co] (post_scale NULL: a bias)] -> [ReLU] ->
+ *     [relu(. + residual)] (residual [B, Co, Ho, Wo], disp_refinement/AnyNet.py:90);
+ *   DMB_PREACT_GATE: Co = 3P; y, y2, y3 receive G_k / ((|G1| + |G2|) + |G3| + 1e-8) as three [B, P, Ho, Wo] tensors
+ *     (out_channels_total = P, out_ch_offset = 0); otherwise y2, y3 are unused.
+ * x (the tensor's base): channels [in_ch_offset, in_ch_offset + Ci) of [B, in_channels_total, D, H, W] (D = 1 for 2-D) are
+ * read; items [B2, B) come from x2 (same layout, item 0 = item B2) when x2 is not NULL: both views of a pair in one launch.
+ * y (the tensor's base): channels [out_ch_offset, out_ch_offset + Co) of [B, out_channels_total, D, Ho, Wo] are written,
+ * Ho = (H' - 1) / stride + 1 with H' = H / 2 when pooling, else H. */
+int dmb_preact_conv_f32(const float* x, const float* x2, int B2, const float* w, const float* pre_scale, const float* pre_shift,
+                        const float* post_scale, const float* post_shift, const float* residual, float* y, float* y2, float* y3,
+                        int B, int Ci, int Co, int D, int H, int W, int ndim, int stride, int flags, int in_channels_total,
+                        int in_ch_offset, int out_channels_total, int out_ch_offset, void* stream);
+
+/* The up-sampled coarse disparity of a warp stage (models/AnyNet.py:84,103 = cost_processors/AnyNet.py:64-70):
+ * up = F.interpolate(low * scale, (H, W), bilinear, align_corners=False), low [B, 1, h, w] -> up [B, 1, H, W]; and, when
+ * samples is not NULL, samples [B, D, H, W] = lin[k] + up (lin: DEVICE [D], the stage's linspace). */
+int dmb_anynet_stage_samples_f32(const float* low, const float* lin, float* up, float* samples, int B, int h, int w, int H,
+                                 int W, int D, float scale, void* stream);
+
+/* c = a + b over n elements (models/AnyNet.py:85,104: up_low_d + high_d). */
+int dmb_add_f32(const float* a, const float* b, float* c, long long n, void* stream);
+
+/* The final maps (models/AnyNet.py:117-118,137-140): d0 .. d3 [B, 1, h_k, w_k] -> out [7, B, 1, H, W]:
+ * out[k] = F.interpolate((d_k * W) / w_k, (H, W), bilinear, align_corners=False) for k < 4, out[3 + k] = out[k - 1] - out[k]. */
+int dmb_anynet_final_maps_f32(const float* d0, const float* d1, const float* d2, const float* d3, const int* h_host,
+                              const int* w_host, float* out, int B, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
