@@ -14,11 +14,13 @@ LIB_DIR = os.path.join(PKG_DIR, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdmb_hip.so")
 INCLUDE = os.path.join(os.path.dirname(PKG_DIR), "include")
 
-SOURCES = ["core.cpp", "volume.hip", "regression.hip", "conv3d.hip", "confhead.hip", "gwc_mfma.hip", "conv2d.hip", "losses.hip", "conv3d_x6.hip", "wgrad.hip", "norm.hip", "path_bwd.hip", "catconv.hip", "warp_volume.hip", "deconv3d_zy.hip", "conv3d_sk.hip", "spn.hip", "preprocess.hip", "preact_conv.hip"]
+SOURCES = ["core.cpp", "volume.hip", "regression.hip", "conv3d.hip", "confhead.hip", "gwc_mfma.hip", "conv2d.hip", "losses.hip", "conv3d_x6.hip", "wgrad.hip", "norm.hip", "path_bwd.hip", "catconv.hip", "warp_volume.hip", "deconv3d_zy.hip", "conv3d_sk.hip", "spn.hip", "preprocess.hip", "preact_conv.hip", "patch_match.hip"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
-# warp_volume.hip restates the reference's FP32 sampler arithmetic operation by operation: no fused multiply-adds there
-EXTRA_FLAGS = {"warp_volume.hip": ["-ffp-contract=off"], "spn.hip": ["-ffp-contract=off"]}
+# warp_volume.hip and patch_match.hip restate the reference's FP32 sampler arithmetic (warp_taps.h) operation by operation: no
+# fused multiply-adds there
+EXTRA_FLAGS = {"warp_volume.hip": ["-ffp-contract=off"], "spn.hip": ["-ffp-contract=off"], "patch_match.hip": ["-ffp-contract=off"]}
+SHARED_HEADERS = ["dmb_common.h", "interp.h", "warp_taps.h"]
 
 
 def _hipcc():
@@ -35,7 +37,7 @@ def sources_digest(dev=False, defs=""):
     a stale one, or one that travelled to another box with different sources -- is refused instead of silently used."""
     import hashlib
     h = hashlib.sha256()
-    for name in SOURCES + ["dmb_common.h", "interp.h"]:
+    for name in SOURCES + SHARED_HEADERS:
         h.update(name.encode())
         h.update(open(os.path.join(CSRC, name), "rb").read())
     h.update(open(os.path.join(INCLUDE, "dmb_hip.h"), "rb").read())
@@ -78,7 +80,7 @@ def build_library(force=False, verbose=True, dev=False):
     if tag:
         lib_path = os.path.join(LIB_DIR, "libdmb_hip_dev_%s.so" % tag)
         suffix, extra = ".dev_%s.o" % tag, extra + os.environ.get("DMB_BUILD_DEFS", "").split()
-    headers = [os.path.join(CSRC, "dmb_common.h"), os.path.join(CSRC, "interp.h"), os.path.join(INCLUDE, "dmb_hip.h")]
+    headers = [os.path.join(CSRC, h) for h in SHARED_HEADERS] + [os.path.join(INCLUDE, "dmb_hip.h")]
     # the build id: a generated translation unit that returns the digest of the sources this library is linked from.  If the
     # digest recorded by the previous build differs (whatever the file times say -- a checkout, a copied tree), everything is rebuilt.
     digest = sources_digest(dev, os.environ.get("DMB_BUILD_DEFS", "") if tag else "")

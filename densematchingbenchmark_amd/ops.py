@@ -1937,4 +1937,72 @@ def anynet_final_maps(disps, size):
     return list(out.unbind(0))
 
 
+# ---------------------------------------------------------------------------------------------- DeepPruner's sampler
+PATCH_MATCH_MAX_SAMPLES = 85      # include/dmb_hip.h: DMB_PATCH_MATCH_MAX_SAMPLES
+MAX_DISP_SAMPLES = 256            # include/dmb_hip.h: DMB_MAX_DISP_SAMPLES
+
+
+def _range_maps(min_disparity, max_disparity, B, H, W, what):
+    maps = []
+    for t, n in ((min_disparity, "min_disparity"), (max_disparity, "max_disparity")):
+        t = _f32c(t, n)
+        if tuple(t.shape) != (B, 1, H, W):
+            raise _lib.DmbLibraryError("%s: %s must be [%d, 1, %d, %d], got %s" % (what, n, B, H, W, tuple(t.shape)))
+        maps.append(t)
+    return maps
+
+
+def patch_match_step(left, right, noise, min_disparity=None, max_disparity=None, vertical=False, temperature=7.0,
+                     bounds=(0.0, 0.0), want_noise=True, out=None):
+    """One propagate + evaluate half-iteration of PatchMatch (disp_samplers/utils/patch_match.py:329-356), filter size 3.
+
+    ``noise`` [B, P, H, W]; the range is the pair of [B, 1, H, W] maps, or -- both None -- the constants ``bounds`` on every
+    pixel.  Returns (samples, new_noise).  ``out`` None: samples is a new [B, P, H, W]; ``out`` a [B, P + 2, H, W] tensor: the
+    samples land in its channels 1 .. P, the range's ends in channels 0 and P + 1, and it is returned.  ``want_noise`` False:
+    no new noise is written (the last half-iteration), new_noise is None."""
+    lib = _lib.load()
+    left, right = _feature_pair(left, right, "patch_match_step")
+    noise = _f32c(noise, "noise")
+    B, C, H, W = left.shape
+    if noise.dim() != 4 or noise.shape[0] != B or tuple(noise.shape[2:]) != (H, W):
+        raise _lib.DmbLibraryError("patch_match_step: noise must be [%d, P, %d, %d], got %s" % (B, H, W, tuple(noise.shape)))
+    P = noise.shape[1]
+    if (min_disparity is None) != (max_disparity is None):
+        raise _lib.DmbLibraryError("patch_match_step: give both range maps or neither")
+    lo = hi = None
+    if min_disparity is not None:
+        lo, hi = _range_maps(min_disparity, max_disparity, B, H, W, "patch_match_step")
+    if out is None:
+        res = torch.empty((B, P, H, W), dtype=torch.float32, device=left.device)
+        ctot, coff, ends = P, 0, 0
+    else:
+        res = out
+        if res.dtype != torch.float32 or not res.is_contiguous() or tuple(res.shape) != (B, P + 2, H, W):
+            raise _lib.DmbLibraryError("patch_match_step: out must be a contiguous float32 [%d, %d, %d, %d]" % (B, P + 2, H, W))
+        ctot, coff, ends = P + 2, 1, 1
+    new_noise = torch.empty_like(noise) if want_noise else None
+    check(lib.dmb_patch_match_step_f32(dev_ptr(left), dev_ptr(right), dev_ptr(noise), dev_ptr(lo, allow_none=True),
+                                       dev_ptr(hi, allow_none=True), float(bounds[0]), float(bounds[1]),
+                                       dev_ptr(new_noise, allow_none=True), dev_ptr(res), B, C, P, H, W, int(bool(vertical)),
+                                       float(temperature), ctot, coff, ends, stream_ptr(left.device)), "dmb_patch_match_step_f32")
+    return res, new_noise
+
+
+def deeppruner_uniform_samples(min_disparity, max_disparity, sample_number, max_disp=None):
+    """disp_samplers/DeepPruner.py:99-115: ``sample_number`` samples per pixel, both ends of the range included, [B, N, H, W];
+    with ``max_disp`` the range head of stage "post" (:48-66) runs first, in the same launch."""
+    lib = _lib.load()
+    lo = _f32c(min_disparity, "min_disparity")
+    if lo.dim() != 4 or lo.shape[1] != 1:
+        raise _lib.DmbLibraryError("deeppruner_uniform_samples: min_disparity must be [B, 1, H, W], got %s" % (tuple(lo.shape),))
+    B, _, H, W = lo.shape
+    lo, hi = _range_maps(lo, max_disparity, B, H, W, "deeppruner_uniform_samples")
+    N = int(sample_number)
+    out = torch.empty((B, N, H, W), dtype=torch.float32, device=lo.device)
+    check(lib.dmb_deeppruner_uniform_samples_f32(dev_ptr(lo), dev_ptr(hi), dev_ptr(out), B, H, W, N, int(max_disp is not None),
+                                                 float(max_disp if max_disp is not None else 0.0), stream_ptr(lo.device)),
+          "dmb_deeppruner_uniform_samples_f32")
+    return out
+
+
 from .spn import GateRecurrent2dnoind  # noqa: E402,F401  (``dmb.ops.GateRecurrent2dnoind``: dmb/ops/__init__.py:1)

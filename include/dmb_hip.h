@@ -656,6 +656,39 @@ int dmb_add_f32(const float* a, const float* b, float* c, long long n, void* str
 int dmb_anynet_final_maps_f32(const float* d0, const float* d1, const float* d2, const float* d3, const int* h_host,
                               const int* w_host, float* out, int B, int H, int W, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * DeepPruner's disparity sampler (disp_samplers/DeepPruner.py, disp_samplers/utils/patch_match.py), forward only
+ * ---------------------------------------------------------------------------------------- */
+
+#define DMB_PATCH_MATCH_MAX_SAMPLES 85 /* intervals P of one PatchMatch step: 3P planes <= DMB_MAX_DISP_SAMPLES */
+
+/* One propagate + evaluate half-iteration of differentiable PatchMatch with a propagation filter of size 3
+ * (patch_match.py:119-174, 218-253, 329-356).  Per pair b, interval p < P and pixel:
+ *   n_j   = noise_in[b, p] at x-1, x, x+1 (vertical == 0) or y-1, y, y+1 (vertical != 0); 0 outside the image
+ *   s_j   = (max - min) * (float)(1 / (P + 1)) * n_j + (min + (max - min) * ((float)(p + 1) / (float)(P + 1)))
+ *   c_j   = mean_c(L[b, c] * T_j[c]) * temperature,  T_j = the warp of dmb_fast_cat_fms_f32 at sample s_j on plane
+ *           k = 3p + j of a volume of D = 3P planes (so the first and last plane keep half their weight)
+ *   prob  = softmax_j(c_j);  sample = sum_j prob_j * s_j;  noise = sum_j prob_j * n_j
+ * L, R: [B, C, H, W];  noise_in: [B, P, H, W];  min_disp, max_disp: [B, 1, H, W], or both NULL: the constants min_const,
+ * max_const on every pixel (the "pre" stage's full range).  noise_out: [B, P, H, W] or NULL, never noise_in (neighbours
+ * read the previous half-iteration).  out: NULL, or the base of [B, out_channels_total, H, W] whose channels
+ * [out_ch_offset, out_ch_offset + P) receive the samples; write_ends != 0: channel out_ch_offset - 1 receives min and
+ * channel out_ch_offset + P receives max (patch_match.py:359 without the concatenation).
+ * The sampler's arithmetic is the reference's FP32 operation for operation; the channel sum is four interleaved ascending
+ * chains, the same for any B and launch size.  1 <= P <= DMB_PATCH_MATCH_MAX_SAMPLES, any C >= 1, H, W >= 2:
+ * DMB_EUNSUPPORTED otherwise. */
+int dmb_patch_match_step_f32(const float* L, const float* R, const float* noise_in, const float* min_disp,
+                             const float* max_disp, float min_const, float max_const, float* noise_out, float* out, int B,
+                             int C, int P, int H, int W, int vertical, float temperature, int out_channels_total,
+                             int out_ch_offset, int write_ends, void* stream);
+
+/* DeepPruner.py:99-115 (UniformSampler): out [B, N, H, W], out[:, 0] = min, out[:, N - 1] = max,
+ * out[:, k] = min + (max - min) * ((float)k / (float)(N - 1)); range_head != 0: preceded by DeepPruner.py:48-66, stage
+ * "post" -- order the two maps, stretch ranges narrower than N by their shortfall, halve, clamp to [0, max_disp_limit].
+ * Elementwise FP32 in the reference's order of operations: bit-exact.  2 <= N <= DMB_MAX_DISP_SAMPLES. */
+int dmb_deeppruner_uniform_samples_f32(const float* min_disp, const float* max_disp, float* out, int B, int H, int W, int N,
+                                       int range_head, float max_disp_limit, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
