@@ -1,0 +1,1 @@
+from .hw_hourglass import HWHourglass  # noqa: F401

@@ -55,22 +55,39 @@ def epoch_on_mode_switch(module, mode):
 class FusedConv3d(nn.Sequential):
     """Sequential(Conv3d | ConvTranspose3d, [BatchNorm3d], [ReLU]) executed as one fused HIP kernel.
 
-    kernel 3 / padding 1 / stride 1|2 convolutions and kernel 3 / stride 2 / padding 1 / output_padding 1
-    transposed convolutions (the only forms the aggregators use).  ``forward(x, residual=None)`` computes
-    ``act(BN(conv(x)) + residual)`` where ``act`` is ReLU iff the unit has one or ``relu=True`` is passed
-    (hourglass.py:67-70,78-81 apply the ReLU after the skip add)."""
+    kernel 3 / padding 1 convolutions with stride 1, 2 or (1, 2, 2), and kernel 3 / padding 1 transposed convolutions with
+    stride 2 / output_padding 1 or stride (1, 2, 2) / output_padding (0, 1, 1) (the only forms the aggregators use; ``stride``
+    and ``output_padding`` may be ints or 3-tuples, (1, 1, 1) meaning 1 as hw_hourglass.py:36-39 writes it).
+    ``forward(x, residual=None)`` computes ``act(BN(conv(x)) + residual)`` where ``act`` is ReLU iff the unit has one or
+    ``relu=True`` is passed (hourglass.py:67-70,78-81 apply the ReLU after the skip add).
+
+    The (1, 2, 2) forms and the 16-output-channel forms (DeepPruner's HWHourglass, csrc/conv3d_hw.hip) are inference-only."""
+
+    HW = (1, 2, 2)
 
     def __init__(self, batch_norm, in_planes, out_planes, kernel_size=3, stride=1, padding=1, dilation=1, bias=True,
                  relu=False, transposed=False, output_padding=0):
         layers = []
+        stride = self._triple(stride)
+        output_padding = self._triple(output_padding)
         if transposed:
-            if (kernel_size, stride, padding, output_padding) != (3, 2, 1, 1):
-                raise NotImplementedError("HIP transposed conv: only kernel 3, stride 2, padding 1, output_padding 1")
+            form = (kernel_size, stride, padding, output_padding)
+            if form == (3, self.HW, 1, (0, 1, 1)):
+                if out_planes not in (16, 32, 64):
+                    raise NotImplementedError("HIP transposed conv with stride (1, 2, 2): 16, 32 or 64 output channels, got %d"
+                                              % out_planes)
+            elif form != (3, 2, 1, 1):
+                raise NotImplementedError("HIP transposed conv: only kernel 3, padding 1 with stride 2, output_padding 1 or "
+                                          "stride (1, 2, 2), output_padding (0, 1, 1)")
             layers.append(nn.ConvTranspose3d(in_planes, out_planes, kernel_size, stride=stride, padding=padding,
                                              output_padding=output_padding, bias=bias))
         else:
-            if kernel_size != 3 or padding != 1 or dilation != 1 or stride not in (1, 2):
-                raise NotImplementedError("HIP conv3d: only kernel 3, padding 1, dilation 1, stride 1 or 2")
+            if kernel_size != 3 or padding != 1 or dilation != 1 or stride not in (1, 2, self.HW):
+                raise NotImplementedError("HIP conv3d: only kernel 3, padding 1, dilation 1, stride 1, 2 or (1, 2, 2)")
+            if stride == self.HW and out_planes not in (16, 32, 64, 128):
+                raise NotImplementedError("HIP conv3d with stride (1, 2, 2): 16, 32, 64 or 128 output channels, got %d" % out_planes)
+            if stride == 2 and out_planes == 16:
+                raise NotImplementedError("HIP conv3d: 16 output channels with stride 1 or (1, 2, 2) only")
             layers.append(nn.Conv3d(in_planes, out_planes, kernel_size, stride=stride, padding=padding,
                                     dilation=dilation, bias=bias))
         if batch_norm:
@@ -80,6 +97,18 @@ class FusedConv3d(nn.Sequential):
         super().__init__(*layers)
         self.in_planes, self.out_planes, self.stride = in_planes, out_planes, stride
         self.transposed, self.has_bn, self.has_relu = transposed, bool(batch_norm), bool(relu)
+        # the forms of csrc/conv3d_hw.hip: no backward, never the bf16x6 path
+        self.hw_form = stride == self.HW or (out_planes == 16 and not (transposed and stride == 2))
+
+    @staticmethod
+    def _triple(v):
+        """An int, or a 3-tuple collapsed to an int when its entries agree ((1, 1, 1) -> 1)."""
+        if isinstance(v, (tuple, list)):
+            v = tuple(int(e) for e in v)
+            if len(v) != 3:
+                raise NotImplementedError("HIP conv3d: stride / output_padding must be an int or a 3-tuple, got %s" % (v,))
+            return v[0] if v[0] == v[1] == v[2] else v
+        return v
 
     def train(self, mode=True):
         epoch_on_mode_switch(self, mode)
@@ -133,12 +162,19 @@ class FusedConv3d(nn.Sequential):
                 raise ValueError("FusedConv3d: residual and skip are mutually exclusive")
             residual, act = skip, ("pre" if act else False)
         if train_fn.wants_grad(self, x, residual):
+            if self.hw_form:
+                raise NotImplementedError("FusedConv3d: the stride-(1, 2, 2) and 16-output-channel units are inference-only "
+                                          "(no backward); call eval() and run under torch.no_grad()")
             # training / differentiable path: conv, BatchNorm statistics, epilogue and their backward
             # passes as separate HIP launches under torch.autograd
             return train_fn.conv_unit(self, x, residual, act)
         wp, scale, shift = self._prepacked()
         if self.transposed:
+            if self.stride == self.HW:
+                return ops.deconv3d_k3s2(x, wp, self.out_planes, scale, shift, residual, act, stride=self.HW)
             return ops.deconv3d_k3s2(x, wp, self.out_planes, scale, shift, residual, act)
+        if self.hw_form:
+            return ops.conv3d_k3(x, wp, self.out_planes, scale, shift, residual, self.stride, act)
         if ops.conv3d_mode() == "bf16x6" and ops.conv3d_x6_applicable(x, self.out_planes, self.stride):
             return ops.conv3d_k3_x6(x, self._prepacked_x6(), self.out_planes, scale, shift, residual, act)   # opt-in only
         return ops.conv3d_k3(x, wp, self.out_planes, scale, shift, residual, self.stride, act)

@@ -294,7 +294,47 @@ def _out_tensor(out, shape, device, what):
     return out
 
 
+def _hw_stride(stride, what):
+    """A convolution stride as the kernels know it: 1, 2, or "hw" for (1, 2, 2) (the (y, x)-strided family, csrc/conv3d_hw.hip)."""
+    if isinstance(stride, (tuple, list)):
+        stride = tuple(int(s) for s in stride)
+        if stride == (1, 2, 2):
+            return "hw"
+        if stride in ((1, 1, 1), (2, 2, 2)):
+            return stride[0]
+        raise _lib.DmbLibraryError("%s: stride %s is not built: 1, 2 or (1, 2, 2)" % (what, stride))
+    return stride
+
+
+def _conv3d_k3_hw(x, wpack, Co, scale, shift, residual, stride_hw, relu, out):
+    """conv3d_k3's launches on dmb_conv3d_k3_hw_f32 (ctypes only): stride (1, 2, 2), and stride 1 with 16 output channels."""
+    lib = _lib.load()
+    x = _f32c(x, "x")
+    B, Ci, D, H, W = x.shape
+    y = _out_tensor(out, (B, Co, D, (H - 1) // stride_hw + 1, (W - 1) // stride_hw + 1), x.device, "conv3d_k3")
+    if residual is not None and tuple(residual.shape) != tuple(y.shape):
+        raise _lib.DmbLibraryError("residual shape %s != output shape %s" % (tuple(residual.shape), tuple(y.shape)))
+    _affine_ok(scale, shift, Co, "conv3d_k3")
+    if wpack.numel() != lib.dmb_conv3d_packed_floats(Co, Ci):
+        raise _lib.DmbLibraryError("conv3d_k3: packed weights hold %d floats, %d -> %d channels need %d"
+                                   % (wpack.numel(), Ci, Co, lib.dmb_conv3d_packed_floats(Co, Ci)))
+    tag = "conv3d_k3_s%s_%dto%d" % ("122" if stride_hw == 2 else "1", Ci, Co)
+    if _kernel_timer is not None:
+        _kernel_timer.start(tag)
+    check(lib.dmb_conv3d_k3_hw_f32(dev_ptr(x), dev_ptr(wpack), dev_ptr(scale, allow_none=True),
+                                   dev_ptr(shift, allow_none=True), dev_ptr(residual, allow_none=True), dev_ptr(y),
+                                   B, Ci, Co, D, H, W, stride_hw, _relu_mode(relu) | _conv_flags(), stream_ptr(x.device)),
+          "dmb_conv3d_k3_hw_f32")
+    if _kernel_timer is not None:
+        _kernel_timer.stop(tag)
+    return y
+
+
 def conv3d_k3(x, wpack, Co, scale=None, shift=None, residual=None, stride=1, relu=False, out=None):
+    """``stride``: 1, 2, or the tuple (1, 2, 2) ((1, 1, 1) and (2, 2, 2) mean 1 and 2)."""
+    stride = _hw_stride(stride, "conv3d_k3")
+    if stride == "hw" or (stride == 1 and Co == 16):
+        return _conv3d_k3_hw(x, wpack, Co, scale, shift, residual, 2 if stride == "hw" else 1, relu, out)
     sh = _lib.shim()
     if sh is not None:      # the torch-extension shim: the same checks and the same C-ABI call, without the interpreter
         if _kernel_timer is not None:
@@ -702,10 +742,43 @@ def deconv3d_workspace(device):
     return ws
 
 
-def deconv3d_k3s2(x, wpack, Co, scale=None, shift=None, residual=None, relu=False, workspace="auto", out=None, out_width=None):
+def _deconv3d_k3_hw(x, wpack, Co, scale, shift, residual, relu, out):
+    """deconv3d_k3s2's launch on dmb_deconv3d_k3_hw_f32 (ctypes only): stride (1, 2, 2), output_padding (0, 1, 1)."""
+    lib = _lib.load()
+    x = _f32c(x, "x")
+    B, Ci, D, H, W = x.shape
+    y = _out_tensor(out, (B, Co, D, 2 * H, 2 * W), x.device, "deconv3d_k3s2")
+    if residual is not None and tuple(residual.shape) != tuple(y.shape):
+        raise _lib.DmbLibraryError("residual shape %s != output shape %s" % (tuple(residual.shape), tuple(y.shape)))
+    _affine_ok(scale, shift, Co, "deconv3d_k3s2")
+    if wpack.numel() != lib.dmb_deconv3d_packed_floats(Ci, Co):
+        raise _lib.DmbLibraryError("deconv3d_k3s2: packed weights hold %d floats, %d -> %d channels need %d"
+                                   % (wpack.numel(), Ci, Co, lib.dmb_deconv3d_packed_floats(Ci, Co)))
+    tag = "deconv3d_k3_s122_%dto%d" % (Ci, Co)
+    if _kernel_timer is not None:
+        _kernel_timer.start(tag)
+    check(lib.dmb_deconv3d_k3_hw_f32(dev_ptr(x), dev_ptr(wpack), dev_ptr(scale, allow_none=True),
+                                     dev_ptr(shift, allow_none=True), dev_ptr(residual, allow_none=True), dev_ptr(y),
+                                     B, Ci, Co, D, H, W, _relu_mode(relu) | _conv_flags(), stream_ptr(x.device)),
+          "dmb_deconv3d_k3_hw_f32")
+    if _kernel_timer is not None:
+        _kernel_timer.stop(tag)
+    return y
+
+
+def deconv3d_k3s2(x, wpack, Co, scale=None, shift=None, residual=None, relu=False, workspace="auto", out=None, out_width=None,
+                  stride=(2, 2, 2)):
     """``workspace``: "auto" = the per-stream workspace above; None = the kernel form without counters; or an int32 tensor of
     DECONV3D_WORKSPACE_BYTES holding zeros.  ``out_width``: for an input whose rows are zero-padded on the right to a multiple
-    of 4 columns, the real output width (2 x the unpadded input width); default 2 W."""
+    of 4 columns, the real output width (2 x the unpadded input width); default 2 W.  ``stride``: (2, 2, 2) (or 2), or (1, 2, 2)
+    = output_padding (0, 1, 1), y [B, Co, D, 2H, 2W]; that form has no workspace and no padded rows."""
+    stride = tuple(int(s) for s in stride) if isinstance(stride, (tuple, list)) else (int(stride),) * 3
+    if stride == (1, 2, 2):
+        if not (isinstance(workspace, str) and workspace == "auto") or out_width is not None:
+            raise _lib.DmbLibraryError("deconv3d_k3s2: stride (1, 2, 2) takes no workspace and no out_width")
+        return _deconv3d_k3_hw(x, wpack, Co, scale, shift, residual, relu, out)
+    if stride != (2, 2, 2):
+        raise _lib.DmbLibraryError("deconv3d_k3s2: stride %s is not built: (2, 2, 2) or (1, 2, 2)" % (stride,))
     sh = _lib.shim()
     if sh is not None:
         if isinstance(workspace, str):

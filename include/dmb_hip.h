@@ -247,6 +247,27 @@ int dmb_deconv3d_k3s2_f32(const float* x, const float* wpack, const float* scale
                           const float* residual, float* y, int B, int Ci, int Co, int D, int H, int W, int Wout,
                           int relu, void* workspace, void* stream);
 
+/* Conv3d, kernel 3, padding 1, stride 1 along D and stride_hw along H and W (DeepPruner's HWHourglass,
+ * cost_processors/utils/hw_hourglass.py:31-74).  x: [B, Ci, D, H, W]; y: [B, Co, D, (H - 1) / stride_hw + 1,
+ * (W - 1) / stride_hw + 1].  stride_hw == 2 with Co in {16, 32, 64, 128}, or stride_hw == 1 with Co == 16 (the 32 -> 16 layer of
+ * aggregators/DeepPruner.py:36; the other stride-1 widths are dmb_conv3d_k3_f32's).  wpack from dmb_conv3d_pack_weights_f32 (Co =
+ * 16 is its 32-row stream with 16 zero rows).  Any Ci >= 1, any D, H, W >= 1, operands 4-byte aligned.  Epilogue as above.  Every
+ * launch is ONE fma chain per output voxel in the packed stream's order (DMB_CONV_SINGLE_CHAIN is accepted and changes nothing):
+ * a stride-(1, 2, 2) result equals the single-chain stride-1 result at even (y, x) bit for bit, and batch item i equals the item
+ * run alone.  DMB_EINVAL on NULL / non-positive arguments, DMB_EUNSUPPORTED outside the sets above, both before any device call. */
+int dmb_conv3d_k3_hw_f32(const float* x, const float* wpack, const float* scale, const float* shift,
+                         const float* residual, float* y, int B, int Ci, int Co, int D, int H, int W,
+                         int stride_hw, int relu, void* stream);
+
+/* ConvTranspose3d kernel 3, stride (1, 2, 2), padding 1, output_padding (0, 1, 1) (hw_hourglass.py:41-44,56-59,71-74):
+ * x: [B, Ci, D, H, W] -> y: [B, Co, D, 2H, 2W];  y[od, oy, ox] += x[id, iy, ix] * w[kd, ky, kx] with od = id - 1 + kd,
+ * oy = 2 iy - 1 + ky, ox = 2 ix - 1 + kx.  Co in {16, 32, 64}; any Ci >= 1, any D, H, W >= 1, operands 4-byte aligned.  wpack from
+ * dmb_deconv3d_pack_weights_f32.  No workspace: a static tile walk, one fma chain per output voxel (channel pair ascending, the
+ * taps of the voxel's parity class ascending), reproducible and batch-invariant.  Epilogue and error codes as above. */
+int dmb_deconv3d_k3_hw_f32(const float* x, const float* wpack, const float* scale, const float* shift,
+                           const float* residual, float* y, int B, int Ci, int Co, int D, int H, int W, int relu,
+                           void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Cost up-sampling
  * ---------------------------------------------------------------------------------------- */
