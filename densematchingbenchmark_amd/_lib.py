@@ -122,6 +122,8 @@ SIGNATURES = {
     "dmb_anynet_final_maps_f32": (_c_int, [_P] * 4 + [_HI, _HI, _P] + [_c_int] * 3 + [_P]),
     "dmb_patch_match_step_f32": (_c_int, [_P] * 5 + [_c_float, _c_float, _P, _P] + [_c_int] * 6 + [_c_float] + [_c_int] * 3 + [_P]),
     "dmb_deeppruner_uniform_samples_f32": (_c_int, [_P, _P, _P] + [_c_int] * 5 + [_c_float, _P]),
+    "dmb_deeppruner_volume_f32": (_c_int, [_P] * 6 + [_c_int] * 6 + [_P]),
+    "dmb_conv2d_k5_small_f32": (_c_int, [_P] * 5 + [_c_int] * 6 + [_P]),
 }
 
 

@@ -1,0 +1,59 @@
+"""Launching wrappers of csrc/deeppruner_heads.hip (DeepPruner's cost processor): thin, in the manner of ``ops.fast_cat_fms``.
+They live next to ``ops`` and not in it: ``ops``'s public launching functions are an enumerated set (each has its memory-contract
+cases in tests/test_memory_contract_gpu.py); these two have theirs in tests/test_memory_contract_deeppruner_gpu.py.  No fallback."""
+import torch
+
+from . import _lib
+from .ops import _f32c, _feature_pair, _same_shape, check, dev_ptr, stream_ptr
+
+K5_MAX_C = 16                    # include/dmb_hip.h: DMB_CONV2D_K5_MAX_C
+MAX_FEATURE_PLANES = 85          # include/dmb_hip.h: DMB_PATCH_MATCH_MAX_SAMPLES
+
+
+def deeppruner_volume(left, right, disp_sample, min_feature=None, max_feature=None):
+    """DeepPruner.py:192-195,204-208 in one launch: [B, C, H, W] x 2, samples [B, D, H, W] and, for stage "post", the two range
+    feature maps [B, P, H, W] -> [B, 2C + 1 + 2P, D, H, W] = cat(fast_cat_fms(left, right, samples), samples, min_feature on every
+    plane, max_feature on every plane), bit for bit, each element written once."""
+    lib = _lib.load()
+    left, right = _feature_pair(left, right, "deeppruner_volume")
+    B, C, H, W = left.shape
+    ds = _f32c(disp_sample, "disp_sample")
+    if ds.dim() != 4 or ds.shape[0] != B or tuple(ds.shape[2:]) != (H, W):
+        raise _lib.DmbLibraryError("deeppruner_volume: disp_sample must be [B, D, H, W] matching the features, got %s" % (tuple(ds.shape),))
+    D, P = ds.shape[1], 0
+    if (min_feature is None) != (max_feature is None):
+        raise _lib.DmbLibraryError("deeppruner_volume: min_feature and max_feature come together or not at all")
+    if min_feature is not None:
+        min_feature, max_feature = _f32c(min_feature, "min_feature"), _f32c(max_feature, "max_feature")
+        _same_shape(min_feature, max_feature, "deeppruner_volume features")
+        if min_feature.dim() != 4 or min_feature.shape[0] != B or tuple(min_feature.shape[2:]) != (H, W) or min_feature.shape[1] < 1:
+            raise _lib.DmbLibraryError("deeppruner_volume: the range features must be [B, P, H, W] matching the image features, got %s"
+                                       % (tuple(min_feature.shape),))
+        P = min_feature.shape[1]
+    out = torch.empty((B, 2 * C + 1 + 2 * P, D, H, W), dtype=torch.float32, device=left.device)
+    check(lib.dmb_deeppruner_volume_f32(dev_ptr(left), dev_ptr(right), dev_ptr(ds), dev_ptr(min_feature, allow_none=True),
+                                        dev_ptr(max_feature, allow_none=True), dev_ptr(out), B, C, D, H, W, P,
+                                        stream_ptr(left.device)), "dmb_deeppruner_volume_f32")
+    return out
+
+
+def conv2d_k5_small(x, w, scale=None, shift=None, relu=False):
+    """nn.Conv2d(Ci, Co, 5, stride 1, padding 2) on 1 .. 16 channels: x [B, Ci, H, W], w [Co, Ci, 5, 5] as it is -> [B, Co, H, W];
+    epilogue acc * scale[co] + shift[co] (``scale`` None: acc + shift[co], a bias; both None: acc), then ReLU if ``relu``."""
+    lib = _lib.load()
+    x, w = _f32c(x, "x"), _f32c(w, "w")
+    if x.dim() != 4 or w.dim() != 4 or tuple(w.shape[1:]) != (x.shape[1], 5, 5):
+        raise _lib.DmbLibraryError("conv2d_k5_small: x [B, Ci, H, W] and w [Co, Ci, 5, 5] expected, got %s and %s"
+                                   % (tuple(x.shape), tuple(w.shape)))
+    B, Ci, H, W = x.shape
+    Co = w.shape[0]
+    for t, n in ((scale, "scale"), (shift, "shift")):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != Co):
+            raise _lib.DmbLibraryError("conv2d_k5_small: %s must hold %d float32 values" % (n, Co))
+    scale = scale.contiguous() if scale is not None else None
+    shift = shift.contiguous() if shift is not None else None
+    y = torch.empty((B, Co, H, W), dtype=torch.float32, device=x.device)
+    check(lib.dmb_conv2d_k5_small_f32(dev_ptr(x), dev_ptr(w), dev_ptr(scale, allow_none=True), dev_ptr(shift, allow_none=True),
+                                      dev_ptr(y), B, Ci, Co, H, W, 1 if relu else 0, stream_ptr(x.device)),
+          "dmb_conv2d_k5_small_f32")
+    return y

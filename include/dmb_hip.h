@@ -710,6 +710,32 @@ int dmb_patch_match_step_f32(const float* L, const float* R, const float* noise_
 int dmb_deeppruner_uniform_samples_f32(const float* min_disp, const float* max_disp, float* out, int B, int H, int W, int N,
                                        int range_head, float max_disp_limit, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * DeepPruner's cost processor (cost_processors/DeepPruner.py), forward only: csrc/deeppruner_heads.hip
+ * ---------------------------------------------------------------------------------------- */
+
+/* The raw cost volume of DeepPruner.py:192-195,204-208 in one pass; every element of out is written exactly once.
+ * L, R: [B, C, H, W];  sample: [B, D, H, W];  out: [B, 2C + 1 + 2P, D, H, W]:
+ *   channels [0, 2C)            what dmb_fast_cat_fms_f32(per_pixel = 1) writes: L * (T > 0) and T, T = R warped by -sample
+ *   channel  2C                 sample[b, k, y, x]
+ *   channels [2C + 1, +P)       min_feat[b, p, y, x] on every plane k            (min_feat, max_feat: [B, P, H, W])
+ *   the next P                  max_feat[b, p, y, x] on every plane k
+ * P == 0 with min_feat == max_feat == NULL: stage "pre", 2C + 1 channels.  The sampler arithmetic is warp_taps.h's, the rest
+ * are copies: bit-identical to the composition.  Any C >= 1; D, H, W >= 2 and P <= DMB_PATCH_MATCH_MAX_SAMPLES
+ * (DMB_EUNSUPPORTED otherwise); operands 4-byte aligned. */
+int dmb_deeppruner_volume_f32(const float* L, const float* R, const float* sample, const float* min_feat, const float* max_feat,
+                              float* out, int B, int C, int D, int H, int W, int P, void* stream);
+
+#define DMB_CONV2D_K5_MAX_C 16
+
+/* nn.Conv2d(Ci, Co, 5, stride 1, padding 2) on 1 .. DMB_CONV2D_K5_MAX_C input and output channels (DMB_EUNSUPPORTED otherwise).
+ * x: [B, Ci, H, W];  w: the nn weight [Co, Ci, 5, 5] as it is;  y: [B, Co, H, W];  any H, W >= 1; operands 4-byte aligned.
+ *   each output: ONE ascending (ci, ky, kx) fmaf chain from 0 -- independent of the launch size, so batch item i equals the
+ *     same item run alone bit for bit;
+ *   epilogue: acc * scale[co] + shift[co] | acc + shift[co] (scale NULL: a bias) | acc (both NULL), then ReLU if relu != 0. */
+int dmb_conv2d_k5_small_f32(const float* x, const float* w, const float* scale, const float* shift, float* y, int B, int Ci,
+                            int Co, int H, int W, int relu, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
