@@ -12,6 +12,7 @@
 // Input and output may be channel windows of wider tensors (the 320-channel SPP concat is written in place).
 #include <type_traits>
 
+#include "bilinear_hp.h"
 #include "dmb_common.h"
 
 // Workgroups per CU the kernel is built for (build-time experiment knob, build.py DMB_BUILD_DEFS): LDS budget per workgroup,
@@ -503,8 +504,8 @@ __global__ __launch_bounds__(256) void bilinear_ac_kernel(const float* __restric
 }
 
 // F.interpolate(mode='bilinear', align_corners=False) * mult (disp_refinement/StereoNet.py:49-50, edge_aware.py:49-50:
-// the coarse disparity map up-sampled to image size and rescaled by the resolution ratio).  ATen's source index:
-// src = max(scale * (dst + 0.5) - 0.5, 0), scale = in / out in FP32.
+// the coarse disparity map up-sampled to image size and rescaled by the resolution ratio).  ATen's source index, the weights
+// and the blend are bilinear_hp.h's, which the fused refinement head (refine_head.hip) shares.
 __global__ __launch_bounds__(256) void bilinear_hp_kernel(const float* __restrict__ x, float* __restrict__ y, int C, int Hi,
                                                           int Wi, int Ho, int Wo, float sh, float sw, float mult,
                                                           int out_ctot, int out_coff) {
@@ -513,18 +514,11 @@ __global__ __launch_bounds__(256) void bilinear_hp_kernel(const float* __restric
   const int b = blockIdx.y;
   if (i >= (long long)C * Ho * Wo) return;
   const int xo = (int)(i % Wo), yo = (int)((i / Wo) % Ho), c = (int)(i / ((long long)Wo * Ho));
-  const float sy = fmaxf(sh * ((float)yo + 0.5f) - 0.5f, 0.f), sx = fmaxf(sw * ((float)xo + 0.5f) - 0.5f, 0.f);
-  int y0 = (int)sy, x0 = (int)sx;
-  y0 = y0 > Hi - 1 ? Hi - 1 : y0;
-  x0 = x0 > Wi - 1 ? Wi - 1 : x0;
-  const int y1 = y0 + (y0 < Hi - 1 ? 1 : 0), x1 = x0 + (x0 < Wi - 1 ? 1 : 0);
-  float ly = sy - (float)y0, lx = sx - (float)x0;
-  ly = fminf(fmaxf(ly, 0.f), 1.f);
-  lx = fminf(fmaxf(lx, 0.f), 1.f);
+  const HpTap ty = hp_tap(yo, Hi, sh), tx = hp_tap(xo, Wi, sw);
   const float* p = x + ((size_t)b * C + c) * Hi * Wi;
-  const float a0 = fmaf(p[(size_t)y0 * Wi + x1], lx, p[(size_t)y0 * Wi + x0] * (1.f - lx));
-  const float a1 = fmaf(p[(size_t)y1 * Wi + x1], lx, p[(size_t)y1 * Wi + x0] * (1.f - lx));
-  y[(((size_t)b * out_ctot + out_coff + c) * Ho + yo) * Wo + xo] = fmaf(a1, ly, a0 * (1.f - ly)) * mult;
+  const float* p0 = p + (size_t)ty.i0 * Wi;
+  const float* p1 = p + (size_t)ty.i1 * Wi;
+  y[(((size_t)b * out_ctot + out_coff + c) * Ho + yo) * Wo + xo] = hp_blend(p0[tx.i0], p0[tx.i1], p1[tx.i0], p1[tx.i1], tx.l, ty.l, mult);
 }
 
 template <class C>
@@ -801,7 +795,7 @@ extern "C" int dmb_bilinear_scale_f32(const float* x, float* y, int B, int C, in
       out_ch_offset + C > out_channels_total || B > 65535)
     return fail(DMB_EINVAL, "bilinear_scale: bad argument");
   const long long n = (long long)C * Ho * Wo;
-  const float sh = (float)Hi / (float)Ho, sw = (float)Wi / (float)Wo;
+  const float sh = hp_scale(Hi, Ho), sw = hp_scale(Wi, Wo);
   hipLaunchKernelGGL(bilinear_hp_kernel, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, (hipStream_t)stream, x, y, C, Hi,
                      Wi, Ho, Wo, sh, sw, mult, out_channels_total, out_ch_offset);
   return launch_status("bilinear_scale launch failed");

@@ -11,6 +11,18 @@ from ..layers import train_fn
 from ..layers.basic_layers_2d import BasicBlock, conv_bn, conv_bn_relu
 
 
+def make_layer(bn, in_planes, out_planes, blocks, stride, padding, dilation):
+    """``blocks`` BasicBlocks, the first one strided and with a 1x1 skip convolution where the shape changes (PSMNet.py:64-81;
+    backbones/DeepPruner.py has the same)."""
+    downsample = None
+    if stride != 1 or in_planes != out_planes:
+        downsample = conv_bn(bn, in_planes, out_planes, kernel_size=1, stride=stride, padding=0, dilation=1)
+    layers = [BasicBlock(bn, in_planes, out_planes, stride, downsample, padding, dilation)]
+    for _ in range(1, blocks):
+        layers.append(BasicBlock(bn, out_planes, out_planes, 1, None, padding, dilation))
+    return nn.Sequential(*layers)
+
+
 class PSMNetBackbone(nn.Module):
     def __init__(self, in_planes=3, batch_norm=True):
         super().__init__()
@@ -31,18 +43,18 @@ class PSMNetBackbone(nn.Module):
         self.lastconv = nn.Sequential(conv_bn_relu(bn, 320, 128, 3, 1, 1, 1, bias=False), _BareConv1x1(128, 32))
 
     def _make_layer(self, bn, out_planes, blocks, stride, padding, dilation):
-        downsample = None
-        if stride != 1 or self.in_planes != out_planes:
-            downsample = conv_bn(bn, self.in_planes, out_planes, kernel_size=1, stride=stride, padding=0, dilation=1)
-        layers = [BasicBlock(bn, self.in_planes, out_planes, stride, downsample, padding, dilation)]
+        layer = make_layer(bn, self.in_planes, out_planes, blocks, stride, padding, dilation)
         self.in_planes = out_planes
-        for _ in range(1, blocks):
-            layers.append(BasicBlock(bn, self.in_planes, out_planes, 1, None, padding, dilation))
-        return nn.Sequential(*layers)
+        return layer
 
     def _forward(self, x):
+        return self._features(x)
+
+    def _features(self, x, keep_half=False):
+        """The network; ``keep_half`` (DeepPruner's best backbone, which is this one): also return layer1's output
+        [B, 32, H/2, W/2], as ``(feature, [output_2_1])`` (backbones/DeepPruner.py:122)."""
         x = self.firstconv(x)
-        x = self.layer1(x)
+        x = half = self.layer1(x)
         B, _, H2, W2 = x.shape
         H4, W4 = (H2 - 1) // 2 + 1, (W2 - 1) // 2 + 1
         # PSMNet.py:119-121: cat(output_4_0 [64], output_8 [128], branch4, branch3, branch2, branch1 [32 each])
@@ -61,7 +73,8 @@ class PSMNetBackbone(nn.Module):
             k = branch[0].kernel_size[0]
             pooled = ops.avgpool2d(feat, k, in_window=(64, 128))
             ops.bilinear_ac(branch[1](pooled), (H4, W4), out=feat, out_ch_offset=off)
-        return self.lastconv[1](self.lastconv[0](feat))
+        feature = self.lastconv[1](self.lastconv[0](feat))
+        return (feature, [half]) if keep_half else feature
 
     def _forward_train(self, x):
         """The same network on plain tensors under autograd (SURVEY 8-f3 widened to the backbone): PSMNet.py:64-125."""

@@ -1,9 +1,11 @@
 from ...registry import instantiate
+from .DeepPruner import DeepPrunerBestBackbone, DeepPrunerFastBackbone
 from .GCNet import GCNetBackbone
 from .PSMNet import PSMNetBackbone
 from .StereoNet import StereoNetBackbone
 
-BACKBONES = {"PSMNet": PSMNetBackbone, "StereoNet": StereoNetBackbone, "GCNet": GCNetBackbone}
+BACKBONES = {"PSMNet": PSMNetBackbone, "StereoNet": StereoNetBackbone, "GCNet": GCNetBackbone,
+             "BestDeepPruner": DeepPrunerBestBackbone, "FastDeepPruner": DeepPrunerFastBackbone}
 
 
 def build_backbone(cfg):

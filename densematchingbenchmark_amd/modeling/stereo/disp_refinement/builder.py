@@ -1,11 +1,12 @@
 """Registry of the disparity refinements on the HIP path (the reference's disp_refinement/builder.py:5-9 also lists
-DeepPruner and AnyNet, which are out of scope here)."""
+AnyNet, whose refinement is reached through its own model here)."""
 from ...registry import instantiate
+from .DeepPruner import DeepPrunerRefinement
 from .StereoNet import StereoNetRefinement
 
-REFINEMENTS = dict(StereoNet=StereoNetRefinement)
+REFINEMENTS = dict(StereoNet=StereoNetRefinement, DeepPruner=DeepPrunerRefinement)
 
 
 def build_disp_refinement(cfg):
-    return instantiate(REFINEMENTS, cfg.model.disp_refinement, "disparity refinement", off_path=("DeepPruner", "AnyNet"),
+    return instantiate(REFINEMENTS, cfg.model.disp_refinement, "disparity refinement", off_path=("AnyNet",),
                        batch_norm=cfg.model.batch_norm)

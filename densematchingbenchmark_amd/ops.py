@@ -454,9 +454,17 @@ def warm_packed_parameters(module):
     module.__dict__["_dmb_warmed"] = stamp
 
 
+def _map_tensors(f, out):
+    """``f`` on every tensor of ``out``: a tensor, or tuples / lists of such, nested (``(feature, [low-level maps])``)."""
+    if torch.is_tensor(out):
+        return f(out)
+    return type(out)(_map_tensors(f, o) for o in out)
+
+
 def two_view_forward(fn, left, right, module=None):
     """``(fn(left), fn(right))`` for a per-image function (an eval-mode backbone): the right view on a side stream of the device,
     forked from and joined back into the caller's stream with events; ``ops.set_view_streams(False)``: one batch of both views.
+    ``fn`` returns one tensor, or tuples / lists of tensors, nested, every one with the batch in front.
     ``module``: the nn.Module ``fn`` evaluates.  Its packed-weight caches are filled on the CALLER's stream before the fork:
     filled lazily inside ``fn(right)`` they would be written by pack kernels on the side stream while ``fn(left)`` -- which finds
     the host-side cache entry already present -- reads them on the caller's stream with nothing ordering the two (cold caches:
@@ -464,7 +472,7 @@ def two_view_forward(fn, left, right, module=None):
     if not (_view_streams and left.is_cuda):
         B = left.shape[0]
         f = fn(torch.cat((left, right), 0))
-        return f[:B], f[B:]
+        return _map_tensors(lambda t: t[:B], f), _map_tensors(lambda t: t[B:], f)
     if module is not None:
         warm_packed_parameters(module)
     main = torch.cuda.current_stream(left.device)
@@ -473,7 +481,7 @@ def two_view_forward(fn, left, right, module=None):
     with torch.cuda.stream(side):
         side.wait_event(fork)
         fr = fn(right)
-        fr.record_stream(main)          # allocated on the side stream, consumed on the caller's
+        _map_tensors(lambda t: t.record_stream(main), fr)   # allocated on the side stream, consumed on the caller's
         right.record_stream(side)       # ... and the caller's input is read there
         done = side.record_event()
     fl = fn(left)

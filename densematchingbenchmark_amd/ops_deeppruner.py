@@ -1,6 +1,8 @@
-"""Launching wrappers of csrc/deeppruner_heads.hip (DeepPruner's cost processor): thin, in the manner of ``ops.fast_cat_fms``.
-They live next to ``ops`` and not in it: ``ops``'s public launching functions are an enumerated set (each has its memory-contract
-cases in tests/test_memory_contract_gpu.py); these two have theirs in tests/test_memory_contract_deeppruner_gpu.py.  No fallback."""
+"""Launching wrappers of csrc/deeppruner_heads.hip (DeepPruner's cost processor) and csrc/refine_head.hip (the tail of its
+refinement): thin, in the manner of ``ops.fast_cat_fms``.  They live next to ``ops`` and not in it: ``ops``'s public launching
+functions are an enumerated set (each has its memory-contract cases in tests/test_memory_contract_gpu.py); the first two have
+theirs in tests/test_memory_contract_deeppruner_gpu.py, ``refine_head_up2`` in tests/test_memory_contract_refine_gpu.py.
+No fallback."""
 import torch
 
 from . import _lib
@@ -8,6 +10,7 @@ from .ops import _f32c, _feature_pair, _same_shape, check, dev_ptr, stream_ptr
 
 K5_MAX_C = 16                    # include/dmb_hip.h: DMB_CONV2D_K5_MAX_C
 MAX_FEATURE_PLANES = 85          # include/dmb_hip.h: DMB_PATCH_MATCH_MAX_SAMPLES
+REFINE_HEAD_MAX_C = 16           # include/dmb_hip.h: DMB_REFINE_HEAD_MAX_C
 
 
 def deeppruner_volume(left, right, disp_sample, min_feature=None, max_feature=None):
@@ -56,4 +59,24 @@ def conv2d_k5_small(x, w, scale=None, shift=None, relu=False):
     check(lib.dmb_conv2d_k5_small_f32(dev_ptr(x), dev_ptr(w), dev_ptr(scale, allow_none=True), dev_ptr(shift, allow_none=True),
                                       dev_ptr(y), B, Ci, Co, H, W, 1 if relu else 0, stream_ptr(x.device)),
           "dmb_conv2d_k5_small_f32")
+    return y
+
+
+def refine_head_up2(x, w, init):
+    """The tail of a DeepPruner refinement stage (disp_refinement/DeepPruner.py:36,40-42,87) in one launch: x [B, Ci, H, W]
+    (1 <= Ci <= 16), w [1, Ci, 3, 3] as it is, init [B, 1, H, W] -> [B, 1, 2H, 2W] =
+    F.interpolate(2 * relu(conv3x3(x, w, padding 1) + init), scale_factor 2, bilinear, align_corners=False)."""
+    lib = _lib.load()
+    x, w, init = _f32c(x, "x"), _f32c(w, "w"), _f32c(init, "init")
+    if x.dim() != 4 or w.dim() != 4 or tuple(w.shape) != (1, x.shape[1], 3, 3):
+        raise _lib.DmbLibraryError("refine_head_up2: x [B, Ci, H, W] and w [1, Ci, 3, 3] expected, got %s and %s"
+                                   % (tuple(x.shape), tuple(w.shape)))
+    B, Ci, H, W = x.shape
+    if Ci < 1 or Ci > REFINE_HEAD_MAX_C:
+        raise _lib.DmbLibraryError("refine_head_up2: 1 .. %d input channels, got %d" % (REFINE_HEAD_MAX_C, Ci))
+    if tuple(init.shape) != (B, 1, H, W):
+        raise _lib.DmbLibraryError("refine_head_up2: init must be [B, 1, H, W] = %s, got %s" % ((B, 1, H, W), tuple(init.shape)))
+    y = torch.empty((B, 1, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
+    check(lib.dmb_refine_head_up2_f32(dev_ptr(x), dev_ptr(w), dev_ptr(init), dev_ptr(y), B, Ci, H, W, stream_ptr(x.device)),
+          "dmb_refine_head_up2_f32")
     return y

@@ -736,6 +736,19 @@ int dmb_deeppruner_volume_f32(const float* L, const float* R, const float* sampl
 int dmb_conv2d_k5_small_f32(const float* x, const float* w, const float* scale, const float* shift, float* y, int B, int Ci,
                             int Co, int H, int W, int relu, void* stream);
 
+#define DMB_REFINE_HEAD_MAX_C 16
+
+/* The tail of a DeepPruner refinement stage (disp_refinement/DeepPruner.py:36,40-42,87) in one launch:
+ *   y[B, 1, 2H, 2W] = up2(2 * relu(conv3x3(x[B, Ci, H, W], w[1, Ci, 3, 3]) + init[B, 1, H, W]))
+ * a 3x3 convolution to one channel (no bias, padding 1), the residual add, the ReLU, the doubling and the half-pixel bilinear
+ * up-sampling by two (F.interpolate(scale_factor=2, mode='bilinear', align_corners=False)).
+ * 1 <= Ci <= DMB_REFINE_HEAD_MAX_C (DMB_EUNSUPPORTED otherwise);  w: the nn weight as it is;  any H, W >= 1; operands 4-byte
+ * aligned; a batch item of x and of y below 2 GiB.
+ *   each refined value: ONE ascending (ci, ky, kx) fmaf chain from 0, then + init, max(., 0) -- independent of the launch size, so
+ *     batch item i equals the same item run alone bit for bit;
+ *   the interpolation is dmb_bilinear_scale_f32's with mult = 2, bit for bit; each output element is written once. */
+int dmb_refine_head_up2_f32(const float* x, const float* w, const float* init, float* y, int B, int Ci, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
