@@ -125,6 +125,7 @@ SIGNATURES = {
     "dmb_deeppruner_volume_f32": (_c_int, [_P] * 6 + [_c_int] * 6 + [_P]),
     "dmb_conv2d_k5_small_f32": (_c_int, [_P] * 5 + [_c_int] * 6 + [_P]),
     "dmb_refine_head_up2_f32": (_c_int, [_P] * 4 + [_c_int] * 4 + [_P]),
+    "dmb_deeppruner_final_maps_f32": (_c_int, [_P] * 3 + [_HI, _HI] + [_P] * 3 + [_c_int] * 6 + [_P]),
 }
 
 

@@ -4,7 +4,7 @@ batch-1 regime the reference publishes its timings in (configs/PSMNet/ResultOfPS
 
 Same arguments, same steps, same ``result.pkl``; what differs is WHERE the steps run.  Images are decoded on the host
 (``data.imread``) and go to the GPU as bytes; crop / pad / normalise is one HIP launch per image (csrc/preprocess.hip); the
-model is ``build_model(cfg)`` of this package (HIP backbone + cost path); its eval-mode forward is, by default, captured once per
+model is ``build_model(cfg)`` of this package (HIP backbone + cost path; ``models.DeepPruner`` for the DeepPruner configs); its eval-mode forward is, by default, captured once per
 input shape in a HIP graph and replayed (``graph="auto"``: graph_runner.wants_graph -- at batch 1 the ~190 launches of a step
 cost the host more than the device, see graph_runner.py); the result is cropped with ``remove_padding`` and written by
 ``result_io.save_result`` in the reference's layout.  ``scale_factor`` other than 1 goes through the library's half-pixel
@@ -59,7 +59,12 @@ def init_model(config, checkpoint=None, device='cuda:0', strict=True):
         config = Config.fromfile(config)
     elif not isinstance(config, ConfigDict):
         raise TypeError('config must be a filename or Config object, but got {}'.format(type(config)))
-    model = build_model(config)
+    if config.model.meta_architecture == "DeepPruner":
+        # reached by import: build_model and the registries refuse the DeepPruner configs (models/DeepPruner.py)
+        from ..modeling.stereo.models import DeepPruner
+        model = DeepPruner(config)
+    else:
+        model = build_model(config)
     if checkpoint is not None:
         ckpt = torch.load(checkpoint, map_location="cpu", weights_only=False) if isinstance(checkpoint, str) else checkpoint
         state = ckpt.get("state_dict", ckpt)

@@ -1,6 +1,6 @@
 """DeepPruner's cost processor: drop-in for cost_processors/DeepPruner.py:11-234 (``ConfidenceRangePredictor`` and
-``DeepPrunerProcessor``), same constructor arguments, attribute names and ``state_dict`` keys.  Reached by import only: the
-registries gain their 'DeepPruner' entries together with the model.
+``DeepPrunerProcessor``), same constructor arguments, attribute names and ``state_dict`` keys.  Reached by import only (the model,
+models/DeepPruner.py, constructs it directly): ``build_cost_processor`` refuses the type.
 
 Launches.  The raw volume of both stages is ONE launch of csrc/deeppruner_heads.hip (``ops_deeppruner.deeppruner_volume``: the
 sampled concatenation volume, the samples and -- stage "post" -- the range features on every plane, each element written once).

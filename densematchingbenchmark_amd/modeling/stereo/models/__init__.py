@@ -1,4 +1,5 @@
 from .AnyNet import AnyNet
+from .DeepPruner import DeepPruner  # noqa: F401  (reached by import: not a registry entry, build_model refuses its configs)
 from .general_stereo_model import GeneralizedStereoModel
 
 _META_ARCHITECTURES = {"GeneralizedStereoModel": GeneralizedStereoModel, "AnyNet": AnyNet}

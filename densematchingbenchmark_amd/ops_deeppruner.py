@@ -1,16 +1,18 @@
-"""Launching wrappers of csrc/deeppruner_heads.hip (DeepPruner's cost processor) and csrc/refine_head.hip (the tail of its
-refinement): thin, in the manner of ``ops.fast_cat_fms``.  They live next to ``ops`` and not in it: ``ops``'s public launching
+"""Launching wrappers of csrc/deeppruner_heads.hip (DeepPruner's cost processor), csrc/refine_head.hip (the tail of its
+refinement) and csrc/deeppruner_final_maps.hip (the model's output tail): thin, in the manner of ``ops.fast_cat_fms``.  They live next to ``ops`` and not in it: ``ops``'s public launching
 functions are an enumerated set (each has its memory-contract cases in tests/test_memory_contract_gpu.py); the first two have
-theirs in tests/test_memory_contract_deeppruner_gpu.py, ``refine_head_up2`` in tests/test_memory_contract_refine_gpu.py.
+theirs in tests/test_memory_contract_deeppruner_gpu.py, ``refine_head_up2`` in tests/test_memory_contract_refine_gpu.py,
+``deeppruner_final_maps`` in tests/test_memory_contract_deeppruner_model_gpu.py.
 No fallback."""
 import torch
 
 from . import _lib
-from .ops import _f32c, _feature_pair, _same_shape, check, dev_ptr, stream_ptr
+from .ops import _f32c, _feature_pair, _same_shape, check, dev_ptr, host_ints, stream_ptr
 
 K5_MAX_C = 16                    # include/dmb_hip.h: DMB_CONV2D_K5_MAX_C
 MAX_FEATURE_PLANES = 85          # include/dmb_hip.h: DMB_PATCH_MATCH_MAX_SAMPLES
 REFINE_HEAD_MAX_C = 16           # include/dmb_hip.h: DMB_REFINE_HEAD_MAX_C
+FINAL_MAPS_MAX_K = 3             # include/dmb_hip.h: dmb_deeppruner_final_maps_f32 takes 1 .. 3 list maps
 
 
 def deeppruner_volume(left, right, disp_sample, min_feature=None, max_feature=None):
@@ -80,3 +82,31 @@ def refine_head_up2(x, w, init):
     check(lib.dmb_refine_head_up2_f32(dev_ptr(x), dev_ptr(w), dev_ptr(init), dev_ptr(y), B, Ci, H, W, stream_ptr(x.device)),
           "dmb_refine_head_up2_f32")
     return y
+
+
+def deeppruner_final_maps(disps, min_disparity, max_disparity, size):
+    """The output tail of the DeepPruner model (models/DeepPruner.py:82-94,115) in one launch: ``disps``, the refinement's list of
+    K = 1 .. 3 maps [B, 1, h_k, w_k] (better first, the last one the processor's own disparity), and the two range maps
+    [B, 1, h, w] brought to ``size`` = (H, W) as up(d) = F.interpolate((d * W) / w_d, size, bilinear, align_corners=False).
+    Returns K + 4 contiguous [B, 1, H, W] views of one tensor: up(d_0) .. up(d_{K-1}) = D, (Mn * W) / W, (Mx * W) / W with
+    Mn = up(min_disparity) and Mx = up(max_disparity), |D - Mn| and |Mx - D|."""
+    lib = _lib.load()
+    ds = [_f32c(d, "disp") for d in disps]
+    K = len(ds)
+    if K < 1 or K > FINAL_MAPS_MAX_K:
+        raise _lib.DmbLibraryError("deeppruner_final_maps: 1 .. %d maps in the list, got %d" % (FINAL_MAPS_MAX_K, K))
+    lo, hi = _f32c(min_disparity, "min_disparity"), _f32c(max_disparity, "max_disparity")
+    _same_shape(lo, hi, "deeppruner_final_maps range maps")
+    B = ds[0].shape[0]
+    if any(t.dim() != 4 or t.shape[0] != B or t.shape[1] != 1 or t.shape[2] < 1 or t.shape[3] < 1 for t in ds + [lo]):
+        raise _lib.DmbLibraryError("deeppruner_final_maps: every map must be [B, 1, h, w] with one B, got %s"
+                                   % ([tuple(t.shape) for t in ds + [lo]],))
+    H, W = (int(v) for v in size)
+    if H < 1 or W < 1:
+        raise _lib.DmbLibraryError("deeppruner_final_maps: the output size must be positive, got %s" % ((H, W),))
+    out = torch.empty((K + 4, B, 1, H, W), dtype=torch.float32, device=ds[0].device)
+    ptrs = [dev_ptr(d) for d in ds] + [None] * (FINAL_MAPS_MAX_K - K)
+    check(lib.dmb_deeppruner_final_maps_f32(*ptrs, host_ints([d.shape[2] for d in ds]), host_ints([d.shape[3] for d in ds]),
+                                            dev_ptr(lo), dev_ptr(hi), dev_ptr(out), K, B, lo.shape[2], lo.shape[3], H, W,
+                                            stream_ptr(out.device)), "dmb_deeppruner_final_maps_f32")
+    return list(out.unbind(0))

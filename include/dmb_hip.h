@@ -749,6 +749,22 @@ int dmb_conv2d_k5_small_f32(const float* x, const float* w, const float* scale, 
  *   the interpolation is dmb_bilinear_scale_f32's with mult = 2, bit for bit; each output element is written once. */
 int dmb_refine_head_up2_f32(const float* x, const float* w, const float* init, float* y, int B, int Ci, int H, int W, void* stream);
 
+/* The output tail of the DeepPruner model (models/DeepPruner.py:82-94,115) in one launch.  With
+ *   up(d) = F.interpolate((d * W) / w_d, (H, W), mode='bilinear', align_corners=False)
+ * -- the multiply and the IEEE division are two FP32 roundings applied to each tap before the blend, which is
+ * dmb_bilinear_scale_f32's with mult = 1 -- and d0 .. d{K-1}: [B, 1, h_host[k], w_host[k]] the refinement's list (better first, the
+ * last one the cost processor's own disparity), min_disp, max_disp: [B, 1, h, w], out: [K + 4, B, 1, H, W]:
+ *   out[k] = up(d_k), k < K;  D = out[K - 1], Mn = up(min_disp), Mx = up(max_disp)
+ *   out[K] = (Mn * W) / W,  out[K + 1] = (Mx * W) / W      (the reference interpolates the full-size maps a second time)
+ *   out[K + 2] = |D - Mn|,  out[K + 3] = |Mx - D|          (from the un-rescaled Mn and Mx)
+ * bit-identical to the composition of dmb_bilinear_scale_f32 and elementwise launches; each element of out is written once.
+ * 1 <= K <= 3 (DMB_EUNSUPPORTED otherwise; d_k with k >= K is not read and may be NULL); every extent >= 1; operands 4-byte
+ * aligned; a batch item of every map below 2 GiB (DMB_EUNSUPPORTED otherwise).  Nothing depends on the launch size: batch item i
+ * equals the same item run alone bit for bit. */
+int dmb_deeppruner_final_maps_f32(const float* d0, const float* d1, const float* d2, const int* h_host, const int* w_host,
+                                  const float* min_disp, const float* max_disp, float* out, int K, int B, int h, int w, int H,
+                                  int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
