@@ -17,9 +17,10 @@ DEV_BUILD = os.environ.get("DMB_LIB", "").startswith("dev")    # "dev" or "dev_<
 LIB_PATH = os.path.join(_PKG, "lib", "libdmb_hip_%s.so" % os.environ["DMB_LIB"] if DEV_BUILD else "libdmb_hip.so")
 DECONV3D_WORKSPACE_BYTES = 2048   # include/dmb_hip.h: DMB_DECONV3D_WORKSPACE_BYTES
 CONV_SINGLE_CHAIN = 0x100         # include/dmb_hip.h: DMB_CONV_SINGLE_CHAIN
+DEEPPRUNER_LOSS_WORKSPACE_DOUBLES = 9216   # include/dmb_hip.h: DMB_DEEPPRUNER_LOSS_WORKSPACE_DOUBLES
 HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "dmb_hip.h")
 
-_c_int, _c_float, _c_void_p, _c_ll = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_longlong
+_c_int, _c_float, _c_void_p, _c_ll, _c_double = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_double
 _P = _c_void_p  # device pointer
 _HI = ctypes.POINTER(ctypes.c_int)  # host int array
 _HF = ctypes.POINTER(ctypes.c_float)  # host float array
@@ -126,6 +127,10 @@ SIGNATURES = {
     "dmb_conv2d_k5_small_f32": (_c_int, [_P] * 5 + [_c_int] * 6 + [_P]),
     "dmb_refine_head_up2_f32": (_c_int, [_P] * 4 + [_c_int] * 4 + [_P]),
     "dmb_deeppruner_final_maps_f32": (_c_int, [_P] * 3 + [_HI, _HI] + [_P] * 3 + [_c_int] * 6 + [_P]),
+    "dmb_deeppruner_loss_fwd_f32": (_c_int, [_P] * 3 + [_HI, _HI] + [_P] * 6 + [_c_int] * 6 + [_c_float] * 4 + [_c_double, _P]),
+    "dmb_deeppruner_loss_bwd_f32": (_c_int, [_P] * 3 + [_HI, _HI] + [_P] * 10 + [_c_int] * 6 + [_c_float] * 4 + [_c_double, _P]),
+    "dmb_quantile_loss_fwd_f32": (_c_int, [_P] * 6 + [_c_int] * 3 + [_c_float] * 2 + [_c_double, _P]),
+    "dmb_quantile_loss_bwd_f32": (_c_int, [_P] * 7 + [_c_int] * 3 + [_c_float] * 2 + [_c_double, _P]),
 }
 
 

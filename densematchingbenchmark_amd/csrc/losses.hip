@@ -11,22 +11,11 @@
 // (deterministic: no floating-point atomics).  HBM-bound: forward reads 4 B per cost element, backward reads 4 B and
 // writes 4 B.
 #include "dmb_common.h"
+#include "loss_terms.h"
 
 #pragma clang fp contract(off)
 
 namespace dmb {
-
-constexpr int LOSS_BLOCK = 256;
-
-__device__ __forceinline__ double block_sum(double v, double* sm) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) sm[wave] = v;
-  __syncthreads();
-  return sm[0] + sm[1] + sm[2] + sm[3];
-}
 
 // Per-pixel target distribution of LaplaceDisp2Prob: p_d = softmax_d(-|s_d - g| / v) * m2 + eps, with
 // g = gt * m1 * m2 (the two masks of stereo_focal_loss.py:80 and disp2prob.py:127-129).  The distribution depends only
@@ -178,7 +167,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void map_loss_fwd_kernel(const float* _
         loss = (double)softplus_neg(x[i]);
       } else {
         const float d = fabsf(x[i] - g);
-        loss = (double)(d < 1.f ? 0.5f * d * d : d - 0.5f);
+        loss = (double)smooth_l1_term(d);
       }
     }
   }

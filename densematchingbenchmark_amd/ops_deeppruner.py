@@ -2,7 +2,9 @@
 refinement) and csrc/deeppruner_final_maps.hip (the model's output tail): thin, in the manner of ``ops.fast_cat_fms``.  They live next to ``ops`` and not in it: ``ops``'s public launching
 functions are an enumerated set (each has its memory-contract cases in tests/test_memory_contract_gpu.py); the first two have
 theirs in tests/test_memory_contract_deeppruner_gpu.py, ``refine_head_up2`` in tests/test_memory_contract_refine_gpu.py,
-``deeppruner_final_maps`` in tests/test_memory_contract_deeppruner_model_gpu.py.
+``deeppruner_final_maps`` in tests/test_memory_contract_deeppruner_model_gpu.py.  The four wrappers of csrc/deeppruner_loss.hip (the
+model's training losses, forward and backward, and the elementwise quantile pair) have theirs in
+tests/test_memory_contract_deeppruner_loss_gpu.py.
 No fallback."""
 import torch
 
@@ -110,3 +112,114 @@ def deeppruner_final_maps(disps, min_disparity, max_disparity, size):
                                             dev_ptr(lo), dev_ptr(hi), dev_ptr(out), K, B, lo.shape[2], lo.shape[3], H, W,
                                             stream_ptr(out.device)), "dmb_deeppruner_final_maps_f32")
     return list(out.unbind(0))
+
+
+def _loss_operands(disps, min_disparity, max_disparity, gt, theta, what):
+    ds = [_f32c(d, "disp") for d in disps]
+    K = len(ds)
+    if K < 1 or K > FINAL_MAPS_MAX_K:
+        raise _lib.DmbLibraryError("%s: 1 .. %d maps in the list, got %d" % (what, FINAL_MAPS_MAX_K, K))
+    lo, hi, gt = _f32c(min_disparity, "min_disparity"), _f32c(max_disparity, "max_disparity"), _f32c(gt, "gt")
+    _same_shape(lo, hi, what + " range maps")
+    if gt.dim() != 4 or gt.shape[1] != 1 or gt.shape[2] < 1 or gt.shape[3] < 1:
+        raise _lib.DmbLibraryError("%s: the ground truth must be [B, 1, H, W], got %s" % (what, tuple(gt.shape)))
+    B = gt.shape[0]
+    if any(t.dim() != 4 or t.shape[0] != B or t.shape[1] != 1 or t.shape[2] < 1 or t.shape[3] < 1 for t in ds + [lo]):
+        raise _lib.DmbLibraryError("%s: every map must be [B, 1, h, w] with the ground truth's B, got %s"
+                                   % (what, [tuple(t.shape) for t in ds + [lo]]))
+    if any(t.device != gt.device for t in ds + [lo, hi]):
+        raise _lib.DmbLibraryError("%s: the maps and the ground truth live on different devices" % what)
+    if not 0.0 < float(theta) < 1.0:
+        raise _lib.DmbLibraryError("%s: theta must lie inside (0, 1), got %r" % (what, theta))
+    return ds, lo, hi, gt
+
+
+def deeppruner_loss_fwd(disps, min_disparity, max_disparity, gt, l1_lower, l1_upper, q_lower, q_upper, theta):
+    """The training losses of the DeepPruner model (models/DeepPruner.py:82-108) in one launch plus the finalising block, on the
+    maps as the model holds them: ``disps`` K = 1 .. 3 maps [B, 1, h_k, w_k], the two range maps [B, 1, h, w], ``gt`` [B, 1, H, W].
+    Returns (``out`` [K + 4] float32, ``stats`` [2] float64): the K + 2 smooth-L1 means of up(d_k), (Mn * W) / W and (Mx * W) / W
+    under l1_lower < gt < l1_upper (0 for an empty mask), the two quantile means of Mn and Mx under q_lower < gt < q_upper (NaN for
+    an empty mask), and the two counts for ``deeppruner_loss_bwd``.  No full-size tensor is written."""
+    lib = _lib.load()
+    ds, lo, hi, gt = _loss_operands(disps, min_disparity, max_disparity, gt, theta, "deeppruner_loss_fwd")
+    K = len(ds)
+    out = torch.empty((K + 4,), dtype=torch.float32, device=gt.device)
+    stats = torch.empty((2,), dtype=torch.float64, device=gt.device)
+    ws = torch.empty((_lib.DEEPPRUNER_LOSS_WORKSPACE_DOUBLES,), dtype=torch.float64, device=gt.device)
+    ptrs = [dev_ptr(d) for d in ds] + [None] * (FINAL_MAPS_MAX_K - K)
+    check(lib.dmb_deeppruner_loss_fwd_f32(*ptrs, host_ints([d.shape[2] for d in ds]), host_ints([d.shape[3] for d in ds]),
+                                          dev_ptr(lo), dev_ptr(hi), dev_ptr(gt), dev_ptr(ws), dev_ptr(out), dev_ptr(stats), K,
+                                          gt.shape[0], lo.shape[2], lo.shape[3], gt.shape[2], gt.shape[3], float(l1_lower),
+                                          float(l1_upper), float(q_lower), float(q_upper), float(theta), stream_ptr(gt.device)),
+          "dmb_deeppruner_loss_fwd_f32")
+    return out, stats
+
+
+def _loss_stats(stats, grad_out, n, device, what):
+    if stats.dtype != torch.float64 or stats.numel() != 2 or stats.device != device or not stats.is_contiguous():
+        raise _lib.DmbLibraryError("%s: stats must be the forward's 2 float64 counts on the maps' device" % what)
+    go = _f32c(grad_out, "grad_out")
+    if go.numel() != n or go.device != device:
+        raise _lib.DmbLibraryError("%s: grad_out must hold %d float32 values on the maps' device, got %s" % (what, n, tuple(go.shape)))
+    return go
+
+
+def deeppruner_loss_bwd(disps, min_disparity, max_disparity, gt, stats, grad_out, l1_lower, l1_upper, q_lower, q_upper, theta):
+    """Backward of ``deeppruner_loss_fwd`` in one launch: ``grad_out`` [K + 4] on the device (never read on the host), ``stats`` the
+    forward's.  Returns ([grad_d0 .. grad_d{K-1}], grad_min, grad_max) with the shapes of the maps, every element written once."""
+    lib = _lib.load()
+    ds, lo, hi, gt = _loss_operands(disps, min_disparity, max_disparity, gt, theta, "deeppruner_loss_bwd")
+    K = len(ds)
+    go = _loss_stats(stats, grad_out, K + 4, gt.device, "deeppruner_loss_bwd")
+    gds = [torch.empty(tuple(d.shape), dtype=torch.float32, device=gt.device) for d in ds]
+    glo = torch.empty(tuple(lo.shape), dtype=torch.float32, device=gt.device)
+    ghi = torch.empty(tuple(hi.shape), dtype=torch.float32, device=gt.device)
+    ptrs = [dev_ptr(d) for d in ds] + [None] * (FINAL_MAPS_MAX_K - K)
+    gptrs = [dev_ptr(g) for g in gds] + [None] * (FINAL_MAPS_MAX_K - K)
+    check(lib.dmb_deeppruner_loss_bwd_f32(*ptrs, host_ints([d.shape[2] for d in ds]), host_ints([d.shape[3] for d in ds]),
+                                          dev_ptr(lo), dev_ptr(hi), dev_ptr(gt), dev_ptr(stats), dev_ptr(go), *gptrs, dev_ptr(glo),
+                                          dev_ptr(ghi), K, gt.shape[0], lo.shape[2], lo.shape[3], gt.shape[2], gt.shape[3],
+                                          float(l1_lower), float(l1_upper), float(q_lower), float(q_upper), float(theta),
+                                          stream_ptr(gt.device)), "dmb_deeppruner_loss_bwd_f32")
+    return gds, glo, ghi
+
+
+def _quantile_operands(min_disparity, max_disparity, gt, theta, what):
+    lo, hi, gt = _f32c(min_disparity, "minEstDisp"), _f32c(max_disparity, "maxEstDisp"), _f32c(gt, "gtDisp")
+    _same_shape(lo, gt, what)
+    _same_shape(hi, gt, what)
+    if gt.dim() != 4 or gt.shape[1] != 1 or gt.numel() < 1:
+        raise _lib.DmbLibraryError("%s: the maps must be [B, 1, H, W], got %s" % (what, tuple(gt.shape)))
+    if lo.device != gt.device or hi.device != gt.device:
+        raise _lib.DmbLibraryError("%s: the maps and the ground truth live on different devices" % what)
+    if not 0.0 < float(theta) < 1.0:
+        raise _lib.DmbLibraryError("%s: theta must lie inside (0, 1), got %r" % (what, theta))
+    return lo, hi, gt
+
+
+def quantile_loss_fwd(min_disparity, max_disparity, gt, q_lower, q_upper, theta):
+    """The two terms of losses/utils/quantile_loss.py:25-37 on maps at the ground truth's size, [B, 1, H, W] each: returns
+    (``out`` [2] float32 = the means of (gt - min) * (theta - [gt - min < 0]) and (gt - max) * ((1 - theta) - [gt - max < 0]) under
+    q_lower < gt < q_upper, NaN for an empty mask; ``stats`` [2] float64 for ``quantile_loss_bwd``)."""
+    lib = _lib.load()
+    lo, hi, gt = _quantile_operands(min_disparity, max_disparity, gt, theta, "quantile_loss_fwd")
+    out = torch.empty((2,), dtype=torch.float32, device=gt.device)
+    stats = torch.empty((2,), dtype=torch.float64, device=gt.device)
+    ws = torch.empty((_lib.DEEPPRUNER_LOSS_WORKSPACE_DOUBLES,), dtype=torch.float64, device=gt.device)
+    check(lib.dmb_quantile_loss_fwd_f32(dev_ptr(lo), dev_ptr(hi), dev_ptr(gt), dev_ptr(ws), dev_ptr(out), dev_ptr(stats),
+                                        gt.shape[0], gt.shape[2], gt.shape[3], float(q_lower), float(q_upper), float(theta),
+                                        stream_ptr(gt.device)), "dmb_quantile_loss_fwd_f32")
+    return out, stats
+
+
+def quantile_loss_bwd(min_disparity, max_disparity, gt, stats, grad_out, q_lower, q_upper, theta):
+    """Backward of ``quantile_loss_fwd``: ``grad_out`` [2] on the device; returns (grad_min, grad_max), every element written once."""
+    lib = _lib.load()
+    lo, hi, gt = _quantile_operands(min_disparity, max_disparity, gt, theta, "quantile_loss_bwd")
+    go = _loss_stats(stats, grad_out, 2, gt.device, "quantile_loss_bwd")
+    glo = torch.empty(tuple(gt.shape), dtype=torch.float32, device=gt.device)
+    ghi = torch.empty(tuple(gt.shape), dtype=torch.float32, device=gt.device)
+    check(lib.dmb_quantile_loss_bwd_f32(dev_ptr(lo), dev_ptr(hi), dev_ptr(gt), dev_ptr(stats), dev_ptr(go), dev_ptr(glo),
+                                        dev_ptr(ghi), gt.shape[0], gt.shape[2], gt.shape[3], float(q_lower), float(q_upper),
+                                        float(theta), stream_ptr(gt.device)), "dmb_quantile_loss_bwd_f32")
+    return glo, ghi

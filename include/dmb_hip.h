@@ -765,6 +765,44 @@ int dmb_deeppruner_final_maps_f32(const float* d0, const float* d1, const float*
                                   const float* min_disp, const float* max_disp, float* out, int K, int B, int h, int w, int H,
                                   int W, void* stream);
 
+/* Doubles of workspace the four loss entry points below use at most (a fixed number of blocks strides over the maps). */
+#define DMB_DEEPPRUNER_LOSS_WORKSPACE_DOUBLES 9216
+
+/* The training losses of the DeepPruner model (models/DeepPruner.py:82-108) on the maps as the model holds them, one launch plus
+ * the finalising block; no full-size tensor is written.  With up(), d0 .. d{K-1}, min_disp, max_disp as for
+ * dmb_deeppruner_final_maps_f32, gt: [B, 1, H, W], Mn = up(min_disp), Mx = up(max_disp) -- bit for bit that entry point's maps:
+ *   loss_out[k]     = mean smooth_l1(up(d_k) - gt), k < K            over l1_lower < gt < l1_upper; 0 where no pixel is valid
+ *   loss_out[K]     = mean smooth_l1((Mn * W) / W - gt),  loss_out[K + 1] the same of Mx
+ *   loss_out[K + 2] = mean (gt - Mn) * (theta - [gt - Mn < 0])        over q_lower < gt < q_upper; NaN where no pixel is valid
+ *   loss_out[K + 3] = mean (gt - Mx) * ((1 - theta) - [gt - Mx < 0])  (losses/utils/quantile_loss.py:25-37; 1 - theta in FP64)
+ * Per-pixel terms FP32, sums FP64 in a fixed order (identical from run to run), no atomics.  stats: 2 doubles, the two counts,
+ * for the backward pass.  workspace: DMB_DEEPPRUNER_LOSS_WORKSPACE_DOUBLES doubles, need not be initialised.
+ * 1 <= K <= 3 and a batch item of every map below 2 GiB (DMB_EUNSUPPORTED otherwise); 0 < theta < 1; operands 4-byte aligned. */
+int dmb_deeppruner_loss_fwd_f32(const float* d0, const float* d1, const float* d2, const int* h_host, const int* w_host,
+                                const float* min_disp, const float* max_disp, const float* gt, double* workspace, float* loss_out,
+                                double* stats, int K, int B, int h, int w, int H, int W, float l1_lower, float l1_upper,
+                                float q_lower, float q_upper, double theta, void* stream);
+
+/* Backward of the above in one launch: grad_out is a DEVICE pointer to the K + 4 weights of loss_out (no host read), stats the
+ * forward's.  grad_d0 .. grad_d{K-1}, grad_min, grad_max have the shapes of the maps; each element is written exactly once (a
+ * gather over the full-size pixels whose taps include it, FP64 accumulation in a fixed order: identical from run to run).
+ * grad_min and grad_max collect the smooth-L1 term and the quantile term.  An empty mask gives zero gradients. */
+int dmb_deeppruner_loss_bwd_f32(const float* d0, const float* d1, const float* d2, const int* h_host, const int* w_host,
+                                const float* min_disp, const float* max_disp, const float* gt, const double* stats,
+                                const float* grad_out, float* grad_d0, float* grad_d1, float* grad_d2, float* grad_min,
+                                float* grad_max, int K, int B, int h, int w, int H, int W, float l1_lower, float l1_upper,
+                                float q_lower, float q_upper, double theta, void* stream);
+
+/* The two quantile terms alone on maps already at the ground truth's size (no rescaling: (d * W) / W is not the identity in FP32).
+ * min_disp, max_disp, gt: [B, 1, H, W];  loss_out[0], loss_out[1]: the means of the two terms as above;  stats, workspace as above. */
+int dmb_quantile_loss_fwd_f32(const float* min_disp, const float* max_disp, const float* gt, double* workspace, float* loss_out,
+                              double* stats, int B, int H, int W, float q_lower, float q_upper, double theta, void* stream);
+
+/* Backward of the above: grad_out is a device pointer to 2 floats; grad_min, grad_max: [B, 1, H, W], every element written once. */
+int dmb_quantile_loss_bwd_f32(const float* min_disp, const float* max_disp, const float* gt, const double* stats,
+                              const float* grad_out, float* grad_min, float* grad_max, int B, int H, int W, float q_lower,
+                              float q_upper, double theta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
