@@ -17,6 +17,7 @@ DEV_BUILD = os.environ.get("DMB_LIB", "").startswith("dev")    # "dev" or "dev_<
 LIB_PATH = os.path.join(_PKG, "lib", "libdmb_hip_%s.so" % os.environ["DMB_LIB"] if DEV_BUILD else "libdmb_hip.so")
 DECONV3D_WORKSPACE_BYTES = 2048   # include/dmb_hip.h: DMB_DECONV3D_WORKSPACE_BYTES
 CONV_SINGLE_CHAIN = 0x100         # include/dmb_hip.h: DMB_CONV_SINGLE_CHAIN
+CONV3D_HEAD_PACKED_FLOATS = 1024  # include/dmb_hip.h: DMB_CONV3D_HEAD_PACKED_FLOATS
 DEEPPRUNER_LOSS_WORKSPACE_DOUBLES = 9216   # include/dmb_hip.h: DMB_DEEPPRUNER_LOSS_WORKSPACE_DOUBLES
 HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "dmb_hip.h")
 
@@ -53,6 +54,10 @@ SIGNATURES = {
     "dmb_deconv3d_pack_weights_f32": (_c_int, [_P, _P, _c_int, _c_int, _P]),
     "dmb_conv3d_k3_f32": (_c_int, [_P, _P, _P, _P, _P, _P] + [_c_int] * 8 + [_P]),
     "dmb_conv3d_k3_c1_f32": (_c_int, [_P, _P, _c_float, _P, _P] + [_c_int] * 6 + [_P]),
+    "dmb_conv3d_k3_head_workspace_floats": (_c_ll, [_c_int] * 4),
+    "dmb_conv3d_k3_head_preferred": (_c_int, [_c_int] * 4),
+    "dmb_conv3d_head_pack_weights_f32": (_c_int, [_P, _P, _P]),
+    "dmb_conv3d_k3_head_f32": (_c_int, [_P] * 5 + [_c_float, _P, _P, _P] + [_c_int] * 6 + [_P]),
     "dmb_deconv3d_k3s2_f32": (_c_int, [_P, _P, _P, _P, _P, _P] + [_c_int] * 8 + [_P, _P]),
     "dmb_conv3d_k3_hw_f32": (_c_int, [_P, _P, _P, _P, _P, _P] + [_c_int] * 8 + [_P]),
     "dmb_deconv3d_k3_hw_f32": (_c_int, [_P, _P, _P, _P, _P, _P] + [_c_int] * 7 + [_P]),

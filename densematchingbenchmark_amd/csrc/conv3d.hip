@@ -114,6 +114,7 @@ template <int CIN_, int COUT_, int TY_, int TX_, int CK_, int WN_, int SCHED_ = 
 struct S1Cfg {
   static constexpr int CIN = CIN_, COUT = COUT_, TY = TY_, TX = TX_, CK = CK_, WN = WN_, SCHED = SCHED_;
   static constexpr bool LIN = LIN_;
+  static constexpr bool HEAD = false;          // S1HeadCfg: the 32 -> 1 classifier head inside the epilogue
   static constexpr int G = G_;                  // row-group width: 0 = flattened tiles, 16 = row pairs, 8 = row quads
   static constexpr bool ROWPAIR = G_ != 0;     // any row-group mapping (takes the 16-byte vector path)
   static constexpr int GR = G_ ? 32 / G_ : 1;  // rows per group
@@ -179,6 +180,21 @@ struct S1Cfg {
   static_assert(!LIN || (ROWPAIR && TY == 3 && TX % 4 == 0 && TX >= 32), "linear tiles: vector path, 3 + 2 staged rows, full-width rows");
   static_assert(!ROWPAIR || ((CK * IPC) % 4 == 0 && NT == 1 && LDS_FLOATS >= 4 * 32 * TR_PITCH), "row-pair staging / scratch");
 };
+
+// HEAD: the 48 x 4 row-pair tile of the 32 -> 32 classifier convolution with the 32 -> 1 head that follows it (PSMNet.py:46-54)
+// inside its epilogue; see conv3d_s1_kernel.  Each workgroup leaves the head's partial sums over its own 4 x 4 x 48 voxels: a
+// 6 x 6 x 50 tile (the voxels + the one-voxel halo their taps reach), summed over overlapping tiles by conv3d_head_finish_kernel.
+struct S1HeadCfg : S1Cfg<0, 32, 4, 48, 2, 1, 1, 16, 0> {
+  static constexpr bool HEAD = true;
+  static constexpr int OZ = TZ + 2, OY = TY + 2, OX = TX + 2;
+  static constexpr int OUT_FLOATS = OZ * OY * OX;   // one workspace slot
+  // LDS row pitch of the tile: the two rows of a pair (GSTR * OP floats apart) start 16 banks apart, like the staged input
+  static constexpr int OP = 56, OPLANE = OY * OP;
+  static_assert(GSTR == 2 && XS == 3 && MT == 6 && OX % 2 == 0 && OX <= OP && (2 * OP) % 32 == 16, "head tile");
+  static_assert(OZ * OPLANE + 64 <= LDS_FLOATS && (OZ * OPLANE) % 4 == 0, "the partial-sum tile lives in the freed chunk buffers");
+};
+constexpr int HEAD_PACKED_FLOATS = 16 * 64;   // 16 A fragments: taps (27, padded to 32) x one channel pair each
+static_assert(HEAD_PACKED_FLOATS == DMB_CONV3D_HEAD_PACKED_FLOATS, "include/dmb_hip.h");
 
 // Epilogue shared by the three MFMA kernels: v = acc*scale + shift (+ residual) (relu) for the 16 accumulator
 // registers of one 32x32 tile; `o` is the voxel offset inside one channel plane, `cstride` the channel stride.
@@ -257,6 +273,7 @@ __global__ __launch_bounds__(256, C::WPE) void conv3d_s1_kernel(const float* __r
     for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(127);
   }
   int t = xcd_remap(blockIdx.x, gridDim.x);
+  const int tile = t;         // (HEAD: the workspace slot)
   const int tx = t % ntx;     // LIN: ntx = 64-voxel runs per plane, nty = 1
   t /= ntx;
   const int ty = t % nty;
@@ -385,6 +402,92 @@ __global__ __launch_bounds__(256, C::WPE) void conv3d_s1_kernel(const float* __r
 
   // ---- epilogue ----
   if (dbg & 1) return;
+  if constexpr (C::HEAD) {
+    // The 32 -> 1 head on the matrix cores, straight from the accumulators:  P[tap][v] = sum_c w_head[c][tap] * act(y[c][v])  is a
+    // GEMM with M = 27 taps (padded to 32), K = 32 channels, N = 32 voxels, and an accumulator tile already IS a stream of B
+    // operands: lane (j, h) holds voxel j and, in register s, channel cd_row(s, h) -- K-step s takes register s of both lane halves
+    // as its channel pair, the head weights are packed in that channel order (`res` = the 16 A fragments of
+    // dmb_conv3d_head_pack_weights_f32).  No transposition, no store of the 32-channel tile.  P[tap][v] belongs to the output voxel
+    // v - (tap - centre): the products are gathered into a 6 x 6 x 50 tile in LDS (the chunk buffers are free) in three phases, one
+    // per dz, in which wave wz adds into plane wz + 2 - dz -- no two waves share a plane -- tap by tap, the two lane halves one
+    // after the other (they hold different taps and may meet at an address; the 32 lanes of a half never do).
+    // Every element so receives its terms in one fixed order.  `y` = the workspace: slot `tile` takes the 1800 partial sums,
+    // contributions to voxels outside the volume included (conv3d_head_finish_kernel drops them).
+    float* ot = lds;                               // [OZ][OY][OP]
+    float* tab = lds + C::OZ * C::OPLANE;          // [h][r]: scale, shift of channel cd_row(r, h)
+    float aw[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) aw[s] = res[s * 64 + lane];
+    for (int i = threadIdx.x; i < C::OZ * C::OPLANE / 4; i += 256) reinterpret_cast<float4*>(ot)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (threadIdx.x < 32) {
+      const int co = cd_row(threadIdx.x & 15, threadIdx.x >> 4);
+      tab[threadIdx.x * 2] = scale ? scale[co] : 1.f;
+      tab[threadIdx.x * 2 + 1] = shift ? shift[co] : 0.f;
+    }
+    __syncthreads();
+    const float lo = relu ? 0.f : -__builtin_inff();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float2 ss = *reinterpret_cast<const float2*>(tab + (h * 16 + r) * 2);
+#pragma unroll
+      for (int mt = 0; mt < C::MT; ++mt) acc[mt][0][r] = fmaxf(fmaf(acc[mt][0][r], ss.x, ss.y), lo);
+    }
+    // the products take over the registers of the accumulator tiles they consume
+#pragma unroll
+    for (int mt = 0; mt < C::MT; ++mt) {
+      const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      f32x16 p = DMB_MFMA(aw[0], acc[mt][0][0], zero);
+#pragma unroll
+      for (int s = 1; s < 16; ++s) p = DMB_MFMA(aw[s], acc[mt][0][s], p);
+      acc[mt][0] = p;
+    }
+    // voxels of a partial tile outside the volume are zero padding for the head, whatever the convolution computed there
+#pragma unroll
+    for (int mt = 0; mt < C::MT; ++mt) {
+      const int gy = y0 + C::row_base(mt / C::XS) + C::GSTR * (j >> 4), gxo = x0 + (mt % C::XS) * 16 + (j & 15);
+      const bool inb = z0 + wz < D && gy < H && gxo < W;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[mt][0][r] = inb ? acc[mt][0][r] : 0.f;
+    }
+    // Plain read-add-write, not LDS atomics (measured: 162 ds_add_f32 per wave held the CU's LDS pipe long enough to stall the
+    // B-fragment reads of the co-resident workgroups).  One tap of one lane half at a time: its six tiles are six distinct
+    // addresses per lane and distinct across the 32 lanes, so they go as one batch; the next tap may meet them at an address
+    // from another lane and must follow in program order (a wave's LDS instructions execute in order; the empty asm keeps the
+    // compiler from moving a tap's reads above the previous tap's writes).
+    float* ob = ot + (wz * C::OY + C::GSTR * (j >> 4)) * C::OP + (j & 15);
+#pragma unroll
+    for (int dz = 0; dz < 3; ++dz) {
+      if (dz) __syncthreads();
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {
+        if (h != hh) continue;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int tap = cd_row(r, hh);
+          if (tap >= 27 || tap / 9 != dz) continue;
+          float cur[C::MT];
+#pragma unroll
+          for (int mt = 0; mt < C::MT; ++mt) {
+            const int o0 = ((2 - dz) * C::OY + C::row_base(mt / C::XS) + 2) * C::OP + (mt % C::XS) * 16 + 2;
+            cur[mt] = ob[o0 - ((tap / 3) % 3) * C::OP - tap % 3];
+          }
+#pragma unroll
+          for (int mt = 0; mt < C::MT; ++mt) {
+            const int o0 = ((2 - dz) * C::OY + C::row_base(mt / C::XS) + 2) * C::OP + (mt % C::XS) * 16 + 2;
+            ob[o0 - ((tap / 3) % 3) * C::OP - tap % 3] = cur[mt] + acc[mt][0][r];
+          }
+          asm volatile("" ::: "memory");
+        }
+      }
+    }
+    __syncthreads();
+    float* wt = y + (size_t)tile * C::OUT_FLOATS;
+    for (int i = threadIdx.x; i < C::OUT_FLOATS / 2; i += 256) {
+      const int rw = i / (C::OX / 2), c2 = i - rw * (C::OX / 2);
+      *reinterpret_cast<float2*>(wt + rw * C::OX + c2 * 2) = *reinterpret_cast<const float2*>(ot + rw * C::OP + c2 * 2);
+    }
+    return;
+  }
   const int gz = z0 + wz;
   float* yb = y + (size_t)b * C::COUT * DHW;
   const float* rb = res ? res + (size_t)b * C::COUT * DHW : nullptr;
@@ -1663,6 +1766,55 @@ __global__ __launch_bounds__(256, 1) void conv3d_c1s_kernel(const float* __restr
 // The accumulation order above is (dz, dy) outer, dx inner PER channel, i.e. tap-ascending within a channel and
 // channels ascending -- identical to the MFMA kernels' k order up to their channel pairing.
 
+// ---------------------------------------------------------------------------------------------------------
+// Fused classifier head (conv3d_s1_kernel on S1HeadCfg): weight pack and the pass that finishes it.
+//   whp[s * 64 + lane] = w[c = cd_row(s, lane >> 5)][tap = lane & 31]   (taps 27 .. 31: zero rows)
+// ---------------------------------------------------------------------------------------------------------
+__global__ void pack_head_weights_kernel(const float* __restrict__ w, float* __restrict__ whp) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= HEAD_PACKED_FLOATS) return;
+  const int lane = i & 63, s = i >> 6, tap = lane & 31;
+  whp[i] = tap < 27 ? w[cd_row(s, lane >> 5) * 27 + tap] : 0.f;
+}
+
+// cost[v] = the partial sums of the (at most eight) tiles whose 6 x 6 x 50 slot covers v, added in ascending tile order, + bias
+// (+ residual).  One voxel per thread: a voxel inside a tile reads one float, one on a tile face two, ... a corner eight.
+__global__ __launch_bounds__(256) void conv3d_head_finish_kernel(const float* __restrict__ ws, const float* __restrict__ res,
+                                                                 float* __restrict__ y, float bias, int D, int H, int W, int ntx,
+                                                                 int nty, int ntz, long long total) {
+  using C = S1HeadCfg;
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int gx = (int)(idx % W);
+  long long q = idx / W;
+  const int gy = (int)(q % H);
+  q /= H;
+  const int gz = (int)(q % D), b = (int)(q / D);
+  const int tz = gz / C::TZ, ty = gy / C::TY, tx = gx / C::TX;
+  const int lz = gz - tz * C::TZ, ly = gy - ty * C::TY, lx = gx - tx * C::TX;
+  float s = 0.f;
+  bool any = false;
+  for (int a = -1; a <= 1; ++a) {
+    const int oz = lz - a * C::TZ + 1;   // where tile tz + a keeps this plane
+    if (oz < 0 || oz >= C::OZ || tz + a < 0 || tz + a >= ntz) continue;
+    for (int c = -1; c <= 1; ++c) {
+      const int oy = ly - c * C::TY + 1;
+      if (oy < 0 || oy >= C::OY || ty + c < 0 || ty + c >= nty) continue;
+      for (int e = -1; e <= 1; ++e) {
+        const int ox = lx - e * C::TX + 1;
+        if (ox < 0 || ox >= C::OX || tx + e < 0 || tx + e >= ntx) continue;
+        const size_t slot = (((size_t)b * ntz + (tz + a)) * nty + (ty + c)) * ntx + (tx + e);
+        const float v = ws[slot * C::OUT_FLOATS + (oz * C::OY + oy) * C::OX + ox];
+        s = any ? s + v : v;
+        any = true;
+      }
+    }
+  }
+  s += bias;
+  if (res) s += res[idx];
+  y[idx] = s;
+}
+
 static long long cdiv_ll(long long a, long long b) { return (a + b - 1) / b; }
 template <class C>
 static int launch_s1(const float* x, const float* wp, const float* scale, const float* shift, const float* res,
@@ -2011,6 +2163,50 @@ extern "C" int dmb_conv3d_k3_bnstats_f32(const float* x, const float* wpack, flo
     case 2: return launch_s1_stats<S1Cfg<0, 32, 4, 32, 2, 1, 1, 16, 0>>(x, wpack, y, stats, B, Ci, D, H, W, st);
     default: return launch_s1_stats<S1Cfg<0, 32, 2, 32, 2, 1, 1, 16, 0>>(x, wpack, y, stats, B, Ci, D, H, W, st);
   }
+}
+
+// ---- 32 -> 32 classifier convolution + its 32 -> 1 head in one launch (+ the finishing pass) -----------------------------------
+// The kernel runs on any volume of 16-byte rows (partial tiles are zero-filled and masked like the plain kernel's);
+// dmb_conv3d_k3_head_preferred tells whether dmb_conv3d_k3_f32 would take the same 48 x 4 row-pair tile for the 32 -> 32 layer alone.
+static bool s1_head_runs(int B, int D, int H, int W) {
+  if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || W % 4 != 0 || DMB_OPT(2) != 0) return false;
+  return (long long)32 * D * H * W * 4 < 0x7fffffffLL;
+}
+extern "C" long long dmb_conv3d_k3_head_workspace_floats(int B, int D, int H, int W) {
+  if (!s1_head_runs(B, D, H, W)) return 0;
+  return s1_blocks32(0, B, D, H, W) * S1HeadCfg::OUT_FLOATS;
+}
+extern "C" int dmb_conv3d_k3_head_preferred(int B, int D, int H, int W) {
+  return s1_head_runs(B, D, H, W) && s1_pick32(B, D, H, W) == 0;
+}
+extern "C" int dmb_conv3d_head_pack_weights_f32(const float* w, float* wpack, void* stream) {
+  if (!w || !wpack) return fail(DMB_EINVAL, "conv3d_head_pack_weights: bad argument");
+  hipLaunchKernelGGL(pack_head_weights_kernel, dim3(HEAD_PACKED_FLOATS / 256), dim3(256), 0, (hipStream_t)stream, w, wpack);
+  return launch_status("conv3d_head_pack_weights launch failed");
+}
+extern "C" int dmb_conv3d_k3_head_f32(const float* x, const float* wpack, const float* scale, const float* shift,
+                                      const float* head_wpack, float bias, const float* residual, float* y, float* workspace,
+                                      int B, int Ci, int D, int H, int W, int relu, void* stream) {
+  using C = S1HeadCfg;
+  if (!x || !wpack || !head_wpack || !y || !workspace || B <= 0 || Ci <= 0 || D <= 0 || H <= 0 || W <= 0)
+    return fail(DMB_EINVAL, "conv3d_head: bad argument");
+  if (relu & DMB_CONV_SINGLE_CHAIN) return fail(DMB_EUNSUPPORTED, "conv3d_head: not a single-chain sum (use dmb_conv3d_k3_f32 + dmb_conv3d_k3_c1_f32)");
+  relu &= 0xff;
+  if (!s1_head_runs(B, D, H, W) || (((uintptr_t)x) & 15) != 0 || (((uintptr_t)workspace) & 7) != 0)
+    return fail(DMB_EUNSUPPORTED, "conv3d_head: 16-byte rows only (W % 4 == 0, x 16-byte aligned, 32 channels of one batch item below 2 GiB), workspace 8-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const int ntx = cdiv(W, C::TX), nty = cdiv(H, C::TY), ntz = cdiv(D, C::TZ);
+  const long long nblk = (long long)B * ntx * nty * ntz, total = (long long)B * D * H * W;
+  if (nblk > 0x7fffffffLL || cdiv_ll(total, 256) > 0x7fffffffLL) return fail(DMB_EUNSUPPORTED, "conv3d_head: grid too large");
+  const size_t lds = (size_t)C::LDS_FLOATS * sizeof(float);
+  DMB_ENSURE_LDS((&conv3d_s1_kernel<C, false>), (size_t)(lds));
+  hipLaunchKernelGGL((conv3d_s1_kernel<C, false>), dim3((unsigned)nblk), dim3(256), lds, st, x, wpack, scale, shift, head_wpack,
+                     workspace, Ci, D, H, W, ntx, nty, ntz, relu, (double*)nullptr);
+  const int rc = launch_status("conv3d_head launch failed");
+  if (rc != DMB_OK) return rc;
+  hipLaunchKernelGGL(conv3d_head_finish_kernel, dim3((unsigned)cdiv_ll(total, 256)), dim3(256), 0, st, workspace, residual, y, bias, D,
+                     H, W, ntx, nty, ntz, total);
+  return launch_status("conv3d_head finishing launch failed");
 }
 
 // Split-K form of the transposed convolution (csrc/conv3d_sk.hip): 0 = no, else its variant.  Units: input-resolution tiles.

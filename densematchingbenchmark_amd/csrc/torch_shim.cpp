@@ -120,6 +120,28 @@ at::Tensor conv3d_k3_c1(const at::Tensor& x, const at::Tensor& w, double bias, c
   return y;
 }
 
+// ---- dmb_conv3d_k3_head_f32 (aggregators/PSMNet.py:44-54,70-72: classifier convolution + head in one launch) --------------------
+at::Tensor conv3d_k3_head(const at::Tensor& x, const at::Tensor& wpack, const c10::optional<at::Tensor>& scale,
+                          const c10::optional<at::Tensor>& shift, const at::Tensor& head_wpack, double bias,
+                          const c10::optional<at::Tensor>& residual, int64_t relu_flags) {
+  f32(x, "x");
+  if (x.dim() != 5) raise("conv3d_k3_head: x must be [B, Ci, D, H, W]");
+  const int64_t B = x.size(0), Ci = x.size(1), D = x.size(2), H = x.size(3), W = x.size(4);
+  affine_ok(scale, shift, 32, "conv3d_k3_head");
+  if (wpack.numel() != dmb_conv3d_packed_floats(32, (int)Ci)) raise("conv3d_k3_head: packed weights do not belong to these channel counts");
+  if (head_wpack.numel() != DMB_CONV3D_HEAD_PACKED_FLOATS) raise("conv3d_k3_head: head weights must come from conv3d_head_pack_weights");
+  const long long wsf = dmb_conv3d_k3_head_workspace_floats((int)B, (int)D, (int)H, (int)W);
+  if (wsf <= 0) raise("conv3d_k3_head: this shape does not take the fused form (use conv3d_k3 + conv3d_k3_c1)");
+  at::Tensor y = at::empty({B, 1, D, H, W}, x.options());
+  if (residual.has_value() && residual->sizes() != y.sizes()) raise("conv3d_k3_head residual: shapes differ");
+  at::Tensor ws = at::empty({(int64_t)wsf}, x.options());
+  chk(dmb_conv3d_k3_head_f32(ptr(x, "x"), ptr(wpack, "wpack"), optr(scale, "scale"), optr(shift, "shift"), ptr(head_wpack, "head_wpack"),
+                             (float)bias, optr(residual, "residual"), y.data_ptr<float>(), ws.data_ptr<float>(), (int)B, (int)Ci, (int)D,
+                             (int)H, (int)W, (int)relu_flags, stream_of(x)),
+      "dmb_conv3d_k3_head_f32");
+  return y;
+}
+
 // ---- dmb_trilinear_ac_soft_argmin_f32 (aggregators/PSMNet.py:74-93 + disp_predictors/faster_soft_argmin.py:46-71) -----------------
 std::vector<at::Tensor> trilinear_ac_soft_argmin(const at::Tensor& x, int64_t Do, int64_t Ho, int64_t Wo, double alpha,
                                                  const std::vector<float>& disp_values) {
@@ -292,6 +314,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv3d_k3", &conv3d_k3);
   m.def("deconv3d_k3s2", &deconv3d_k3s2);
   m.def("conv3d_k3_c1", &conv3d_k3_c1);
+  m.def("conv3d_k3_head", &conv3d_k3_head);
   m.def("trilinear_ac_soft_argmin", &trilinear_ac_soft_argmin);
   m.def("conv2d", &conv2d);
   m.def("copy_window", &copy_window);

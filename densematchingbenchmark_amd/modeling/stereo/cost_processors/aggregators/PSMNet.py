@@ -4,13 +4,14 @@ import torch.nn as nn
 
 from ..... import ops
 from ...layers import train_fn
-from ...layers.basic_layers import HeadConv3d, conv3d_bn, conv3d_bn_relu
+from ...layers.basic_layers import HeadConv3d, classifier_branch, conv3d_bn, conv3d_bn_relu
 from ..utils.hourglass import Hourglass
 
 
 class PSMAggregator(nn.Module):
     """raw_cost [B, in_planes, D/4, H/4, W/4] -> [cost3, cost2, cost1], each [B, max_disp, H, W] (best first).
-    25 fused MFMA conv launches + 3 head convs + 3 trilinear up-samplings; all biases absent (PSMNet.py:31-54)."""
+    25 fused MFMA conv launches + 3 head convs + 3 trilinear up-samplings; all biases absent (PSMNet.py:31-54).  In eval mode the
+    three classifier convolutions carry their head inside their own launch where ``classifier_branch`` allows it."""
 
     accepts_lazy_cat = True   # dres0[0] is a FusedConv3d: it takes a LazyCatVolume (cost_processors/utils/cat_fms.py)
 
@@ -36,9 +37,9 @@ class PSMAggregator(nn.Module):
         out1, pre1, post1 = self.dres2(cost0, None, None, skip=cost0)    # out1 + cost0 fused into conv6
         out2, pre2, post2 = self.dres3(out1, pre1, post1, skip=cost0)
         out3, pre3, post3 = self.dres4(out2, pre2, post2, skip=cost0)
-        cost1 = self.classif1[1](self.classif1[0](out1))
-        cost2 = self.classif2[1](self.classif2[0](out2), residual=cost1)  # classif2(out2) + cost1
-        cost3 = self.classif3[1](self.classif3[0](out3), residual=cost2)
+        cost1 = classifier_branch(self.classif1[0], self.classif1[1], out1)
+        cost2 = classifier_branch(self.classif2[0], self.classif2[1], out2, cost1)  # classif2(out2) + cost1
+        cost3 = classifier_branch(self.classif3[0], self.classif3[1], out3, cost2)
         return cost1, cost2, cost3
 
     def _forward_overlapped(self, raw_cost):
@@ -62,20 +63,20 @@ class PSMAggregator(nn.Module):
         fork1 = main.record_event()
         with torch.cuda.stream(side):
             side.wait_event(fork1)
-            cost1 = self.classif1[1](self.classif1[0](out1))
+            cost1 = classifier_branch(self.classif1[0], self.classif1[1], out1)
             up1 = upsample(cost1)
         out2, pre2, post2 = self.dres3(out1, pre1, post1, skip=cost0)
         fork2 = main.record_event()
         with torch.cuda.stream(side):
             side.wait_event(fork2)
-            cost2 = self.classif2[1](self.classif2[0](out2), residual=cost1)
+            cost2 = classifier_branch(self.classif2[0], self.classif2[1], out2, cost1)
             cost2.record_stream(main)           # allocated on the side stream, read by classif3 on the caller's
             join2 = side.record_event()
             up2 = upsample(cost2)
             done = side.record_event()
         out3, pre3, post3 = self.dres4(out2, pre2, post2, skip=cost0)
         main.wait_event(join2)
-        cost3 = self.classif3[1](self.classif3[0](out3), residual=cost2)
+        cost3 = classifier_branch(self.classif3[0], self.classif3[1], out3, cost2)
         up3 = upsample(cost3)
         main.wait_event(done)
         return [up3, up2, up1]

@@ -10,11 +10,11 @@ gradient) the same units run as autograd Functions on the HIP kernels (train_fn.
 import torch
 import torch.nn as nn
 
-from .... import ops, param_state
+from .... import ops, ops_head, param_state
 from . import train_fn
 
 __all__ = ["FusedConv3d", "HeadConv3d", "HeadDeconv3d", "conv3d_bn", "conv3d_bn_relu", "deconv3d_bn", "deconv3d_bn_relu",
-           "bn_parts", "fold_batch_norm"]
+           "bn_parts", "classifier_branch", "fold_batch_norm"]
 
 
 def fold_batch_norm(bn, conv_bias, out_planes, device):
@@ -211,6 +211,21 @@ class HeadConv3d(nn.Conv3d):
             return 0.0
         # one device->host read per weight load, not per call
         return param_state.cached(self, "_dmb_bias", (self.bias,), lambda: float(self.bias.detach().cpu()[0]))
+
+
+def classifier_branch(unit, head, x, residual=None):
+    """``head(unit(x), residual)`` for a classifier branch (PSMNet.py:44-54,70-72): FusedConv3d 32 -> 32 + BN + ReLU, then
+    HeadConv3d 32 -> 1.  In eval mode with no gradient wanted, exact conv3d arithmetic, split-K semantics on and a launch that
+    takes the 48 x 4 row-pair tile, both layers run as ONE convolution launch whose 32-channel output never reaches memory
+    (ops_head.conv3d_k3_head); otherwise the two launches."""
+    if (isinstance(unit, FusedConv3d) and isinstance(head, HeadConv3d) and torch.is_tensor(x) and x.dim() == 5
+            and unit.out_planes == 32 and head.in_channels == 32 and unit.stride == 1 and not unit.transposed and unit.has_relu
+            and not train_fn.wants_grad(unit, x) and not train_fn.wants_grad(head, x, residual)
+            and ops_head.conv3d_k3_head_applicable(x)):
+        wp, scale, shift = unit._prepacked()
+        hw = param_state.cached(head, "_dmb_packed_head", (head.weight,), lambda: ops_head.pack_conv3d_head_weights(head.weight.detach()))
+        return ops_head.conv3d_k3_head(x, wp, hw, scale, shift, head.bias_value(), residual, True)
+    return head(unit(x), residual=residual)
 
 
 class HeadDeconv3d(nn.ConvTranspose3d):

@@ -229,6 +229,30 @@ int dmb_conv3d_k3_f32(const float* x, const float* wpack, const float* scale, co
 int dmb_conv3d_k3_c1_f32(const float* x, const float* w, float bias, const float* residual, float* y,
                          int B, int Ci, int D, int H, int W, int flags, void* stream);
 
+/* The classifier tail of PSMNet.py:44-54 as one convolution launch + one finishing pass:
+ *   y = conv3d_c1(act(scale * conv3d(x, w) + shift), w_head) + bias (+ residual),   x: [B, Ci, D, H, W] -> y: [B, 1, D, H, W]
+ * The 32-channel tensor between the two layers never reaches memory: the 32 -> 32 kernel applies the head to its accumulator
+ * tiles on the matrix cores and leaves, per 4 x 4 x 48 tile of voxels, the head's partial sums over the 6 x 6 x 50 voxels that
+ * tile reaches in workspace[tile]; the finishing pass adds the (at most eight) partial sums covering a voxel in ascending tile
+ * order.  Reproducible run to run and independent of workgroup placement, but NOT the single fma chain of dmb_conv3d_k3_f32 +
+ * dmb_conv3d_k3_c1_f32 (per tap a chain over channels, then taps, then tiles: the last bits differ); with DMB_CONV_SINGLE_CHAIN
+ * in `relu` the call returns DMB_EUNSUPPORTED.
+ * wpack: dmb_conv3d_pack_weights_f32(w, 32, Ci); head_wpack: DMB_CONV3D_HEAD_PACKED_FLOATS floats from
+ * dmb_conv3d_head_pack_weights_f32 (w_head: raw [1, 32, 3, 3, 3]); scale / shift: 32 floats or NULL; relu: 0 or 1.
+ * workspace: dmb_conv3d_k3_head_workspace_floats(B, D, H, W) floats of caller-owned device memory, 8-byte aligned, fully
+ * overwritten by the launch (the library allocates nothing; calls that may overlap in time need different workspaces).  That
+ * function returns 0 -- and the launch DMB_EUNSUPPORTED -- for volumes without 16-byte rows (W % 4 != 0, x not 16-byte aligned) or
+ * with 32 channels of one batch item at 2 GiB or more.  The kernel's tile is 4 x 4 x 48 voxels whatever the volume;
+ * dmb_conv3d_k3_head_preferred returns 1 where dmb_conv3d_k3_f32 would pick that tile for the 32 -> 32 layer on its own (elsewhere
+ * another tile shape covers the volume in fewer rounds and the two separate launches are the better choice). */
+#define DMB_CONV3D_HEAD_PACKED_FLOATS 1024
+long long dmb_conv3d_k3_head_workspace_floats(int B, int D, int H, int W);
+int dmb_conv3d_k3_head_preferred(int B, int D, int H, int W);
+int dmb_conv3d_head_pack_weights_f32(const float* w_head, float* head_wpack, void* stream);
+int dmb_conv3d_k3_head_f32(const float* x, const float* wpack, const float* scale, const float* shift,
+                           const float* head_wpack, float bias, const float* residual, float* y, float* workspace,
+                           int B, int Ci, int D, int H, int W, int relu, void* stream);
+
 /* ConvTranspose3d kernel 3, stride 2, padding 1, output_padding 1 (hourglass.py:52-60):
  * x: [B, Ci, D, H, W] -> y: [B, Co, 2D, 2H, Wout];  y[o] += x[i] * w[k] with o = 2i - 1 + k.  Co = 64 or any Co <= 32
  * (fewer than 32: zero-padded weight rows, e.g. GC-Net's 1-channel output layer, aggregators/GCNet.py:63-67).
