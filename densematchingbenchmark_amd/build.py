@@ -14,14 +14,14 @@ LIB_DIR = os.path.join(PKG_DIR, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdmb_hip.so")
 INCLUDE = os.path.join(os.path.dirname(PKG_DIR), "include")
 
-SOURCES = ["core.cpp", "volume.hip", "regression.hip", "conv3d.hip", "confhead.hip", "gwc_mfma.hip", "conv2d.hip", "losses.hip", "conv3d_x6.hip", "wgrad.hip", "norm.hip", "path_bwd.hip", "catconv.hip", "warp_volume.hip", "deconv3d_zy.hip", "conv3d_sk.hip", "spn.hip", "preprocess.hip", "preact_conv.hip", "patch_match.hip", "conv3d_hw.hip", "deeppruner_heads.hip", "refine_head.hip", "deeppruner_final_maps.hip", "deeppruner_loss.hip"]
+SOURCES = ["core.cpp", "volume.hip", "regression.hip", "conv3d.hip", "conv3d_s1s2.hip", "deconv3d.hip", "conv3d_c1.hip", "confhead.hip", "gwc_mfma.hip", "conv2d.hip", "losses.hip", "conv3d_x6.hip", "wgrad.hip", "norm.hip", "path_bwd.hip", "catconv.hip", "warp_volume.hip", "deconv3d_zy.hip", "conv3d_sk.hip", "spn.hip", "preprocess.hip", "preact_conv.hip", "patch_match.hip", "conv3d_hw.hip", "deeppruner_heads.hip", "refine_head.hip", "deeppruner_final_maps.hip", "deeppruner_loss.hip"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # warp_volume.hip, patch_match.hip and deeppruner_heads.hip restate the reference's FP32 sampler arithmetic (warp_taps.h) operation
 # by operation: no fused multiply-adds there (the 5x5 convolution of deeppruner_heads.hip writes its fmaf chain out)
 EXTRA_FLAGS = {"warp_volume.hip": ["-ffp-contract=off"], "spn.hip": ["-ffp-contract=off"], "patch_match.hip": ["-ffp-contract=off"],
                "deeppruner_heads.hip": ["-ffp-contract=off"]}
-SHARED_HEADERS = ["dmb_common.h", "interp.h", "warp_taps.h", "bilinear_hp.h", "loss_terms.h"]
+SHARED_HEADERS = ["dmb_common.h", "conv3d_mfma.h", "interp.h", "warp_taps.h", "bilinear_hp.h", "loss_terms.h"]
 
 
 def _hipcc():

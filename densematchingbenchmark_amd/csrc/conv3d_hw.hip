@@ -1,7 +1,7 @@
 // 3-D convolutions that stride the (y, x) plane only: the layers of DeepPruner's HWHourglass
 // (reference cost_processors/utils/hw_hourglass.py:31-74, aggregators/DeepPruner.py:34-37) as FP32 implicit GEMMs.
 //
-//   MODE 0   Conv3d k3 p1 stride 1                                  Co = 16 (the widths 32 / 64 / 128 stay on conv3d.hip)
+//   MODE 0   Conv3d k3 p1 stride 1                                  Co = 16 (the widths 32 / 64 / 128 stay on conv3d_s1s2.hip)
 //   MODE 1   Conv3d k3 p1 stride (1, 2, 2)                          Co = 16, 32, 64, 128
 //   MODE 2   ConvTranspose3d k3 p1 stride (1, 2, 2) out_pad (0,1,1) Co = 16, 32, 64
 //
@@ -12,7 +12,7 @@
 // These launches are small (the deepest level of one 544 x 960 pair is 9 x 17 x 30 = 4590 voxels at 128 channels), so the unit of
 // work is as small as the instruction allows: ONE 32-voxel column tile x ONE 32-channel row tile per wave, every wave running the
 // whole K chain of its tile (one chain per output voxel: pair of channels ascending, tap ascending, the two channels of the pair --
-// the order of the packed stream and of the stride-1 / stride-2 kernels of conv3d.hip, so a (1, 2, 2) result equals the stride-1
+// the order of the packed stream and of the stride-1 / stride-2 kernels of conv3d_s1s2.hip, so a (1, 2, 2) result equals the stride-1
 // result sampled at even (y, x) bit for bit, and a batch item equals the item run alone).  There is no split-K form here.
 //
 // Workgroup = 4 waves = WN row tiles x TZ = 4 / WN consecutive z-slices of one (y, x) patch of G columns x 32 / G rows (G = 32, 16

@@ -1,7 +1,7 @@
 // 3x3x3 convolution (stride 1 or 2) for launches that do NOT fill the chip: the K chain of a tile split over the waves of a
 // workgroup (split-K), round 6.
 //
-// Why.  conv3d_s1_kernel / conv3d_s2_kernel (conv3d.hip) give one wave the whole chain of 27 Ci / 2 MFMAs of its 32 x 32 tiles and
+// Why.  conv3d_s1_kernel / conv3d_s2_kernel (conv3d_s1s2.hip) give one wave the whole chain of 27 Ci / 2 MFMAs of its 32 x 32 tiles and
 // walk the input channels in chunks of two behind a workgroup barrier each.  On a full grid that is the fastest form (0.9 of the
 // FP32 matrix peak); on the deepest levels of the hourglass for ONE small pair (BASELINE configs[0]: [1, 64, 4, 16, 32] = 128 tiles
 // for 1024 SIMDs; hourglass.py:62-86 called as apis/inference.py:191-225 does, one pair per call) a launch takes 31-35 us whatever
@@ -21,7 +21,7 @@
 // in the last bits (and with them batch 1 from batch 4 where this form is picked) -- both are FP32 evaluations of the same
 // convolution; the tests bound them against the FP64 yardstick instead of against each other.
 //
-// Which launches take this form is a cost estimate in dmb_conv3d_k3_f32 (conv3d.hip); conv3d_sk_try returns -1 where the shape
+// Which launches take this form is a cost estimate in dmb_conv3d_k3_f32 (conv3d.hip) and dmb_deconv3d_k3s2_f32 (deconv3d.hip); conv3d_sk_try returns -1 where the shape
 // does not qualify.
 #include "dmb_common.h"
 

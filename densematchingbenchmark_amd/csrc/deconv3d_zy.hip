@@ -4,7 +4,7 @@
 //   y[2i - 1 + k] += x[i] * w[k]  per axis:  an even output o = 2i sees k = 1 from input i; an odd output o = 2i + 1 sees
 //   k = 2 from input i and k = 0 from input i + 1.
 //
-// Why a third form.  deconv3d_kernel (conv3d.hip) gives a work item both y parities: 2 (y) x 2 (x) x 2 column tiles x 16 =
+// Why a third form.  deconv3d_kernel (deconv3d.hip) gives a work item both y parities: 2 (y) x 2 (x) x 2 column tiles x 16 =
 // 128 accumulator registers, so two workgroups per CU is all the register file admits -- and with two waves per SIMD the
 // time both sit in their (vector-issue bound) epilogues at once is lost to the matrix cores (45 % /
 // 44 % / 10.6 % of the time two / one / no wave of a SIMD multiplies).  Here an item owns ONE y parity: 2 (x) x 2 x 16 = 64
@@ -529,7 +529,7 @@ static int launch_zy(const float* x, const float* wp, const float* scale, const 
   return launch_status("deconv3d (z/y-parity items) launch failed");
 }
 
-// Entry for dmb_deconv3d_k3s2_f32 (conv3d.hip): returns -1 when this form does not apply (the caller falls back to
+// Entry for dmb_deconv3d_k3s2_f32 (deconv3d.hip): returns -1 when this form does not apply (the caller falls back to
 // deconv3d_kernel), otherwise the launch status.  Requirements: 16-byte aligned rows (W % 4 == 0, aligned bases), all 32 or
 // 64 output channels real, whole 16-channel chunks and at least two of them, 16 input channels of one batch item and one batch item of the output
 // below 2 GiB (32-bit buffer offsets).

@@ -68,6 +68,7 @@ struct DispVal {
 };
 
 __host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+inline long long cdiv_ll(long long a, long long b) { return (a + b - 1) / b; }
 
 // Workgroup -> tile remap so that consecutive tile ids land on the same XCD (workgroup b is placed on
 // XCD b % 8; each XCD has a private 4 MiB L2, and neighbouring tiles share halo voxels).  Bijective for
@@ -81,7 +82,7 @@ __device__ inline int xcd_remap(int bid, int nblk) {
 
 
 // ------------------------------------------------------------------------------------------------------------------
-// MFMA / LDS-DMA helpers shared by the implicit-GEMM kernels (conv3d.hip, confhead.hip, gwc_mfma.hip)
+// MFMA / LDS-DMA helpers shared by the implicit-GEMM kernels (conv3d_s1s2.hip, deconv3d.hip, confhead.hip, gwc_mfma.hip)
 // ------------------------------------------------------------------------------------------------------------------
 #if defined(__HIPCC__)
 typedef float f32x16 __attribute__((ext_vector_type(16)));

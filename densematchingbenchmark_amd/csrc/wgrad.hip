@@ -547,7 +547,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
     dw[((size_t)co * Ci + ci) * 27 + t] = (float)s;
 }
 
-static long long cdiv_ll(long long a, long long b) { return (a + b - 1) / b; }
 static int wgrad_slots() {
   static int cus = 0;
   if (!cus) {

@@ -1,4 +1,4 @@
-"""Launching wrappers of the fused classifier tail (csrc/conv3d.hip: conv3d_s1_kernel on S1HeadCfg + conv3d_head_finish_kernel).
+"""Launching wrappers of the fused classifier tail (csrc/conv3d_s1s2.hip: conv3d_s1_kernel on S1HeadCfg + conv3d_head_finish_kernel).
 They live next to ``ops`` and not in it, like ``ops_deeppruner``: ``ops``'s public launching functions are an enumerated set with
 their memory-contract cases in tests/test_memory_contract_gpu.py; these have theirs in tests/test_memory_contract_head_gpu.py.
 No fallback."""

@@ -1,12 +1,12 @@
 #!/usr/bin/env python
 """Development aid: compile one csrc/*.hip for gfx950 with -Rpass-analysis=kernel-resource-usage and print a table
-(kernel, VGPRs, AGPRs, SGPRs, spills, scratch, LDS, occupancy).   python scripts/attic/kres.py conv3d.hip [filter]"""
+(kernel, VGPRs, AGPRs, SGPRs, spills, scratch, LDS, occupancy).   python scripts/attic/kres.py conv3d_s1s2.hip [filter]"""
 import os
 import re
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 src = os.path.join(ROOT, "densematchingbenchmark_amd", "csrc", sys.argv[1])
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
 out = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-c", src,

@@ -1,4 +1,4 @@
-"""The fused classifier tail (``ops_head.conv3d_k3_head``: csrc/conv3d.hip, conv3d_s1_kernel on S1HeadCfg + conv3d_head_finish_kernel)
+"""The fused classifier tail (``ops_head.conv3d_k3_head``: csrc/conv3d_s1s2.hip, conv3d_s1_kernel on S1HeadCfg + conv3d_head_finish_kernel)
 against the two launches it replaces (``ops.conv3d_k3`` 32 -> 32 + BN + ReLU, then ``ops.conv3d_k3_c1`` 32 -> 1 + residual).
 
 Shapes, the smallest at which tiles (4 x 4 x 48 voxels) and their one-voxel halos can go wrong:
