@@ -7,8 +7,9 @@ tail (aggregators/PSMNet.py:74-93, disp_predictors/faster_soft_argmin.py:51-75),
 whose forward and backward are HIP kernel launches:
 
   forward   raw = conv(x, w) (+ bias)              the inference kernel without its epilogue
-            scale/shift from batch statistics (training) or the running buffers (eval)      bn_train_stats
-            y = act(raw*scale + shift (+ skip))                                             bn_act
+            y = act(raw*scale + shift (+ skip)) with scale/shift from
+              batch statistics (a BatchNorm in training mode; running buffers updated)     bn_train_fwd
+              the running buffers (a BatchNorm in eval mode), or 1 / 0 (no BatchNorm)       bn_act
   backward  dc, dgamma, dbeta, dskip <- dy                                                  bn_act_bwd
             dw = wgrad(x, dc)                                                               conv3d_k3[s2]_wgrad
             dx = the forward kernel of the adjoint convolution on re-packed weights         conv3d_k3 / deconv3d_k3s2
@@ -167,12 +168,17 @@ def _unit_packs(unit, w):
     return tuple(g.packs(unit, weight))
 
 
+def _bias_as_shift(bias):
+    """(scale, shift) operands that make a convolution kernel add the unit's bias in its epilogue; (None, None) without one."""
+    if bias is None:
+        return None, None
+    return _const(1.0, bias.numel(), bias.device), bias.detach().contiguous()
+
+
 def _conv_raw(unit, x, wpack, bias):
     """The unit's convolution without BatchNorm / activation (+ bias through the kernel's shift operand)."""
     Co = unit.out_planes
-    scale = shift = None
-    if bias is not None:
-        scale, shift = _const(1.0, bias.numel(), bias.device), bias.detach().contiguous()
+    scale, shift = _bias_as_shift(bias)
     if unit.transposed:
         return ops.deconv3d_k3s2(x, wpack, Co, scale, shift, None, False)
     return ops.conv3d_k3(x, wpack, Co, scale, shift, None, unit.stride, False)
@@ -198,15 +204,33 @@ def _batch_stats(bn):
     return bn is not None and (bn.training or bn.running_mean is None or bn.running_var is None)
 
 
+def _bn_momentum(bn):
+    """The factor of nn.BatchNorm's running-buffer update: ``momentum``, or with ``momentum=None`` the cumulative moving
+    average's 1 / (batches seen including this one) -- 0 for a BatchNorm that keeps no running buffers."""
+    if bn.momentum is not None:
+        return bn.momentum
+    return 1.0 / float(int(bn.num_batches_tracked) + 1) if bn.track_running_stats else 0.0
+
+
+def _running_affine(bn, gamma, beta, C, device):
+    """(mean, invstd, scale, shift) of a BatchNorm that normalises with its running buffers and leaves them alone -- eval mode,
+    also inside a model in train() (fine-tuning with frozen statistics) -- or the cached identity of a unit without BatchNorm."""
+    if bn is None:
+        zero, one = _const(0.0, C, device), _const(1.0, C, device)
+        return zero, one, one, zero
+    mean = bn.running_mean.detach().float()
+    invstd = torch.rsqrt(bn.running_var.detach().float() + bn.eps)
+    scale = (gamma.detach() if gamma is not None else torch.ones_like(mean)) * invstd
+    shift = (beta.detach() if beta is not None else torch.zeros_like(mean)) - mean * scale
+    return mean, invstd, scale, shift
+
+
 def _unit_bn_forward(bn, raw, gamma, beta, skip, code, C, device, partials=None):
     """BatchNorm (+ skip, + ReLU) of a unit's raw convolution output -> (y, mean, invstd, scale, shift, batch_stats).  A
     batch-statistics BatchNorm takes the two-launch form (ops.bn_train_fwd: block sums, then one kernel that finishes the
     statistics, updates the running buffers and the batch counter and normalises); running statistics / no BatchNorm: bn_act."""
     if _batch_stats(bn):
-        if bn.momentum is None:   # nn.BatchNorm: cumulative moving average, factor 1 / (batches seen including this one)
-            momentum = 1.0 / float(int(bn.num_batches_tracked) + 1) if bn.track_running_stats else 0.0
-        else:
-            momentum = bn.momentum
+        momentum = _bn_momentum(bn)     # (read before the batch counter below moves)
         nbt = bn.num_batches_tracked if bn.track_running_stats and bn.num_batches_tracked is not None else None
         if nbt is not None and nbt.device != raw.device:
             nbt += 1
@@ -219,26 +243,88 @@ def _unit_bn_forward(bn, raw, gamma, beta, skip, code, C, device, partials=None)
         else:
             y, mean, invstd, scale, shift = ops.bn_train_fwd(raw, *args)
         return y, mean, invstd, scale, shift, True
-    mean, invstd, scale, shift, _ = _bn_forward(bn, False, raw, gamma, beta, C, device)
+    mean, invstd, scale, shift = _running_affine(bn, gamma, beta, C, device)
     y = raw if (bn is None and skip is None and code == 0) else ops.bn_act(raw, scale, shift, skip, _RELU[code])
     return y, mean, invstd, scale, shift, False
 
 
-def _carried_outputs(ctx, y, x, skip, carry_x, carry_skip):
+# ---------------------------------------------------------------------------------------------- the unit skeleton
+# ConvUnitFn (3-D) and Conv2dUnitFn (2-D) are one function of (x, weight, bias, gamma, beta, skip, unit, relu, carry_x, carry_skip)
+# around a different convolution: each holds its forward launch and its choice of gradient launches, the rest is here.
+def _unit_params(unit):
+    """(conv, bn or None, gamma, beta) of a Fused unit; gamma / beta are None without an affine BatchNorm."""
+    bn = unit[1] if unit.has_bn else None
+    affine = bn is not None and bn.affine
+    return unit[0], bn, (bn.weight if affine else None), (bn.bias if affine else None)
+
+
+def _apply_carried(fn, unit, x, residual, relu):
+    """``fn`` (ConvUnitFn | Conv2dUnitFn) on the unit's parameters; inside a carry scope x and the skip operand are replaced
+    by their latest aliases and the aliases this call returns are registered for their next consumer."""
+    conv, _, gamma, beta = _unit_params(unit)
+    reg, x, residual, cx, cs = _carry_plan(x, residual)
+    out = fn.apply(x, conv.weight, conv.bias, gamma, beta, residual, unit, relu, cx, cs)
+    if not (cx or cs):
+        return out
+    for t, alias in zip(((x,) if cx else ()) + ((residual,) if cs else ()), out[1:]):
+        reg[id(t)] = (t, alias)
+    return out[0]
+
+
+def _unit_forward_tail(ctx, unit, raw, x, w, x_in, gamma, beta, bias, skip, relu, carry_x, carry_skip, partials=None):
+    """BatchNorm / activation of the raw convolution output, everything the backward pass needs on ``ctx``, and the outputs:
+    y alone, or (y, x_in, skip) with the inputs handed on as identity outputs (gradient carry, top of this file)."""
+    code = _relu_code(relu)
+    y, mean, invstd, scale, shift, batch_stats = _unit_bn_forward(_unit_params(unit)[1], raw, gamma, beta, skip, code, unit.out_planes,
+                                                                  x.device, partials)
+    ctx.unit, ctx.code, ctx.batch_stats = unit, code, batch_stats
+    ctx.has = (bias is not None, gamma is not None, beta is not None, skip is not None)
     ctx.carry = (bool(carry_x), bool(carry_skip))
+    ctx.save_for_backward(x, w, raw, y if code == 1 and skip is not None else None, scale, shift, mean, invstd)
     if not (carry_x or carry_skip):
         return y
     ctx.set_materialize_grads(False)   # an alias nobody consumed has no gradient: None, not a tensor of zeros
-    return (y,) + ((x,) if carry_x else ()) + ((skip,) if carry_skip else ())
+    return (y,) + ((x_in,) if carry_x else ()) + ((skip,) if carry_skip else ())
 
 
-def _carried_grads(ctx, grads):
-    """(dy, what x's later consumers collected, what skip's later consumers collected) from backward's arguments."""
+def _unit_backward_head(ctx, grads):
+    """The BatchNorm / activation backward -> (dc, what x's later consumers collected or None, the saved x and w, and
+    bn_grads = (dgamma, dbeta, dres, need_dres, scale) for _unit_backward_tail)."""
     g = list(grads)
     dy = g.pop(0)
-    dxa = g.pop(0) if ctx.carry[0] else None
-    dsa = g.pop(0) if ctx.carry[1] else None
-    return dy, dxa, dsa
+    dx_acc = g.pop(0) if ctx.carry[0] else None
+    dres_acc = g.pop(0) if ctx.carry[1] else None    # what skip's later consumers collected
+    x, w, raw, y, scale, shift, mean, invstd = ctx.saved_tensors
+    code, has_skip = ctx.code, ctx.has[3]
+    dy = torch.zeros_like(raw) if dy is None else dy.contiguous()
+    need_dres = has_skip and ctx.needs_input_grad[5]
+    if not need_dres:
+        dres_acc = None
+    dc, dgamma, dbeta, dres = ops.bn_act_bwd(dy, raw, y, scale, shift, mean, invstd, _mask_mode(code, has_skip), ctx.batch_stats,
+                                             want_dres=need_dres and code == 1, dres_acc=dres_acc)
+    if need_dres and code != 1 and dres_acc is None:
+        dres = dy                       # the skip branch joins after the activation (or there is none)
+    return dc, dx_acc, x, w, (dgamma, dbeta, dres, need_dres, scale)
+
+
+def _unit_dbias(batch_stats, scale, dbeta):
+    """The bias gradient, the sum of dc over (batch, voxels), without another pass: dc = scale * (dpre - mean terms), so it is
+    dbeta times scale with running statistics (or no BatchNorm: scale = 1) and exactly zero behind batch statistics (sum xhat = 0:
+    the normalisation removes any constant the bias adds)."""
+    return torch.zeros_like(dbeta) if batch_stats else scale * dbeta
+
+
+def _affine_grads(ctx, has_gamma, has_beta, at, dgamma, dbeta):
+    """(dgamma, dbeta) as backward returns them for inputs ``at``, ``at + 1``: None for one that was None or wants no gradient."""
+    needs = ctx.needs_input_grad
+    return dgamma if has_gamma and needs[at] else None, dbeta if has_beta and needs[at + 1] else None
+
+
+def _unit_backward_tail(ctx, dx, dw, bn_grads):
+    dgamma, dbeta, dres, need_dres, scale = bn_grads
+    has_bias, has_gamma, has_beta, _ = ctx.has
+    dbias = _unit_dbias(ctx.batch_stats, scale, dbeta) if has_bias and ctx.needs_input_grad[2] else None
+    return (dx, dw, dbias) + _affine_grads(ctx, has_gamma, has_beta, 3, dgamma, dbeta) + (dres if need_dres else None, None, None, None, None)
 
 
 class ConvUnitFn(torch.autograd.Function):
@@ -252,7 +338,7 @@ class ConvUnitFn(torch.autograd.Function):
         w = weight.detach().contiguous()
         wp_fwd, wp_bwd = _unit_packs(unit, w)
         C = unit.out_planes
-        bn = unit[1] if unit.has_bn else None
+        bn = _unit_params(unit)[1]
         partials = None
         if (_epilogue_stats and _batch_stats(bn) and bias is None and not unit.transposed and unit.stride == 1 and C == 32):
             # the statistics' block sums come out of the convolution's own epilogue (32-channel stride-1 units: 6 of PSMNet's 25)
@@ -261,31 +347,16 @@ class ConvUnitFn(torch.autograd.Function):
                 raw, partials = fused
         if partials is None:
             raw = _conv_raw(unit, x, wp_fwd, bias)
-        code = _relu_code(relu)
-        y, mean, invstd, scale, shift, batch_stats = _unit_bn_forward(bn, raw, gamma, beta, skip, code, C, x.device, partials)
-        ctx.unit, ctx.code, ctx.batch_stats = unit, code, batch_stats
-        ctx.has = (bias is not None, gamma is not None, beta is not None, skip is not None)
         # (the data-gradient pack belongs to the weight version of THIS forward: autograd forbids changing the weight before the
         # backward pass, and the group only re-packs when a version moved)
         ctx.wp_bwd, ctx.w_version = wp_bwd, weight._version
-        ctx.save_for_backward(x, w, raw, y if code == 1 and skip is not None else None, scale, shift, mean, invstd)
-        return _carried_outputs(ctx, y, x_in, skip, carry_x, carry_skip)
+        return _unit_forward_tail(ctx, unit, raw, x, w, x_in, gamma, beta, bias, skip, relu, carry_x, carry_skip, partials)
 
     @staticmethod
     def backward(ctx, *grads):
-        dy, dx_acc, dres_acc = _carried_grads(ctx, grads)
-        x, w, raw, y, scale, shift, mean, invstd = ctx.saved_tensors
-        unit, code = ctx.unit, ctx.code
-        has_bias, has_gamma, has_beta, has_skip = ctx.has
-        dy = torch.zeros_like(raw) if dy is None else dy.contiguous()
-        need_dres = has_skip and ctx.needs_input_grad[5]
-        if not need_dres:
-            dres_acc = None
-        dc, dgamma, dbeta, dres = ops.bn_act_bwd(dy, raw, y, scale, shift, mean, invstd, _mask_mode(code, has_skip), ctx.batch_stats,
-                                                 want_dres=need_dres and code == 1, dres_acc=dres_acc)
-        if need_dres and code != 1 and dres_acc is None:
-            dres = dy                       # the skip branch joins after the activation (or there is none)
-        dw = dx = dbias = None
+        dc, dx_acc, x, w, bn_grads = _unit_backward_head(ctx, grads)
+        unit = ctx.unit
+        dw = dx = None
         if ctx.needs_input_grad[1]:
             if unit.transposed:
                 dw = ops.deconv3d_k3s2_wgrad(x, dc)
@@ -297,32 +368,12 @@ class ConvUnitFn(torch.autograd.Function):
             wp = ctx.wp_bwd if w._version == ctx.w_version else None
             dx = (ops.deconv3d_k3s2_dgrad(dc, w, residual=dx_acc, wpack=wp) if unit.transposed
                   else ops.conv3d_k3_dgrad(dc, w, unit.stride, tuple(x.shape[2:]), residual=dx_acc, wpack=wp))
-        if has_bias and ctx.needs_input_grad[2]:
-            # sum of dc over (batch, voxels) without another pass: dc = scale * (dpre - mean terms), so it is scale * dbeta
-            # with running statistics (or no BatchNorm: scale = 1) and exactly zero behind batch statistics
-            # (sum xhat = 0: the normalisation removes any constant the bias adds)
-            dbias = torch.zeros_like(dbeta) if ctx.batch_stats else scale * dbeta
-        return (dx, dw, dbias, dgamma if has_gamma and ctx.needs_input_grad[3] else None,
-                dbeta if has_beta and ctx.needs_input_grad[4] else None, dres if need_dres else None, None, None, None, None)
+        return _unit_backward_tail(ctx, dx, dw, bn_grads)
 
 
 def conv_unit(unit, x, residual=None, relu=False):
     """Differentiable forward of a FusedConv3d unit (``relu``: False / True = after the skip add / 'pre' = before it)."""
-    conv = unit[0]
-    bn = unit[1] if unit.has_bn else None
-    gamma = bn.weight if bn is not None and bn.affine else None
-    beta = bn.bias if bn is not None and bn.affine else None
-    reg, x, residual, cx, cs = _carry_plan(x, residual)
-    out = ConvUnitFn.apply(x, conv.weight, conv.bias, gamma, beta, residual, unit, relu, cx, cs)
-    if not (cx or cs):
-        return out
-    i = 1
-    if cx:
-        reg[id(x)] = (x, out[i])
-        i += 1
-    if cs:
-        reg[id(residual)] = (residual, out[i])
-    return out[0]
+    return _apply_carried(ConvUnitFn, unit, x, residual, relu)
 
 
 class CatConvUnitFn(torch.autograd.Function):
@@ -339,14 +390,11 @@ class CatConvUnitFn(torch.autograd.Function):
     def forward(ctx, left, right, weight, bias, gamma, beta, unit, relu, disp_idx, kind):
         left, right = left.contiguous(), right.contiguous()
         w = weight.detach().contiguous()
-        C = unit.out_planes
-        sc = sh = None
-        if bias is not None:
-            sc, sh = _const(1.0, bias.numel(), bias.device), bias.detach().contiguous()
+        sc, sh = _bias_as_shift(bias)
         raw = ops.catconv_first(left, right, len(disp_idx), ops.catconv_pack(w, kind), sc, sh, False)
-        bn = unit[1] if unit.has_bn else None
         code = _relu_code(relu)
-        y, mean, invstd, scale, shift, batch_stats = _unit_bn_forward(bn, raw, gamma, beta, None, code, C, left.device)
+        y, mean, invstd, scale, shift, batch_stats = _unit_bn_forward(_unit_params(unit)[1], raw, gamma, beta, None, code,
+                                                                      unit.out_planes, left.device)
         ctx.unit, ctx.code, ctx.batch_stats, ctx.disp_idx, ctx.kind = unit, code, batch_stats, tuple(disp_idx), kind
         ctx.has = (bias is not None, gamma is not None, beta is not None)
         ctx.save_for_backward(left, right, w, raw, scale, shift, mean, invstd)
@@ -371,18 +419,14 @@ class CatConvUnitFn(torch.autograd.Function):
             dvol = ops.conv3d_k3_dgrad(dc, w, 1)
             dL, dR = ops.cat_fms_bwd(dvol, idx) if ctx.kind == "cat" else ops.dif_fms_bwd(dvol, idx)
         if has_bias and ctx.needs_input_grad[3]:
-            dbias = torch.zeros_like(dbeta) if ctx.batch_stats else scale * dbeta
-        return (dL if ctx.needs_input_grad[0] else None, dR if ctx.needs_input_grad[1] else None, dw, dbias,
-                dgamma if has_gamma and ctx.needs_input_grad[4] else None, dbeta if has_beta and ctx.needs_input_grad[5] else None,
-                None, None, None, None)
+            dbias = _unit_dbias(ctx.batch_stats, scale, dbeta)
+        return ((dL if ctx.needs_input_grad[0] else None, dR if ctx.needs_input_grad[1] else None, dw, dbias)
+                + _affine_grads(ctx, has_gamma, has_beta, 4, dgamma, dbeta) + (None, None, None, None))
 
 
 def cat_conv_unit(unit, lazy, relu=False):
     """Differentiable forward of a FusedConv3d unit on a LazyCatVolume (the caller has checked ops.catconv_applicable)."""
-    conv = unit[0]
-    bn = unit[1] if unit.has_bn else None
-    gamma = bn.weight if bn is not None and bn.affine else None
-    beta = bn.bias if bn is not None and bn.affine else None
+    conv, _, gamma, beta = _unit_params(unit)
     return CatConvUnitFn.apply(lazy.reference_fm, lazy.target_fm, conv.weight, conv.bias, gamma, beta, unit, relu,
                                tuple(lazy.disp_idx), lazy.kind)
 
@@ -567,37 +611,7 @@ class ConfHeadFn(torch.autograd.Function):
         dc, dgamma, dbeta, _ = ops.bn_act_bwd(dh, raw, None, scale, shift, mean, invstd, "pre", ctx.batch_stats)   # mask from raw (_mask_mode)
         dw1 = ops.conv2d_k3_wgrad(cost, dc) if ctx.needs_input_grad[1] else None
         dcost = ops.conv2d_dgrad(dc, w1) if ctx.needs_input_grad[0] else None
-        return (dcost, dw1, dgamma if ctx.has[0] and ctx.needs_input_grad[2] else None,
-                dbeta if ctx.has[1] and ctx.needs_input_grad[3] else None, dw2, None)
-
-
-def _bn_forward(bn, training, raw, gamma, beta, C, device):
-    """Shared by the 2-D / 3-D units: (mean, invstd, scale, shift, batch_stats) for this call, running buffers updated.
-    Batch statistics are used when the BatchNorm module ITSELF is in training mode (as nn.BatchNorm decides): a model in
-    train() whose BatchNorm layers were put in eval() -- fine-tuning with frozen statistics -- normalises with the running
-    buffers and leaves them alone."""
-    del training   # the enclosing unit's flag is not what decides
-    batch_stats = _batch_stats(bn)
-    if batch_stats:
-        if bn.momentum is None:   # nn.BatchNorm: cumulative moving average, factor 1 / (batches seen including this one)
-            momentum = 1.0 / float(int(bn.num_batches_tracked) + 1) if bn.track_running_stats else 0.0
-        else:
-            momentum = bn.momentum
-        mean, invstd, scale, shift = ops.bn_train_stats(raw, gamma.detach() if gamma is not None else None,
-                                                        beta.detach() if beta is not None else None,
-                                                        bn.running_mean if bn.track_running_stats else None,
-                                                        bn.running_var if bn.track_running_stats else None, momentum, bn.eps)
-        if bn.track_running_stats and bn.num_batches_tracked is not None:
-            bn.num_batches_tracked += 1
-    elif bn is not None:
-        mean = bn.running_mean.detach().float()
-        invstd = torch.rsqrt(bn.running_var.detach().float() + bn.eps)
-        scale = (gamma.detach() if gamma is not None else torch.ones_like(mean)) * invstd
-        shift = (beta.detach() if beta is not None else torch.zeros_like(mean)) - mean * scale
-    else:
-        mean = shift = _const(0.0, C, device)
-        invstd = scale = _const(1.0, C, device)
-    return mean, invstd, scale, shift, batch_stats
+        return (dcost, dw1) + _affine_grads(ctx, ctx.has[0], ctx.has[1], 2, dgamma, dbeta) + (dw2, None)
 
 
 def _as3d_weight(w):
@@ -640,38 +654,20 @@ class Conv2dUnitFn(torch.autograd.Function):
                 raise NotImplementedError("training path of FusedConv2d: 5x5 layers are stride 2")
         elif k not in (1, 3) or d not in (1, 2, 4, 8) or (s == 2 and d != 1):
             raise NotImplementedError("training path of FusedConv2d: kernel 1|3, dilation 1|2|4|8, stride 2 only without dilation")
-        sc = sh = None
-        if bias is not None:
-            sc, sh = _const(1.0, bias.numel(), bias.device), bias.detach().contiguous()
+        sc, sh = _bias_as_shift(bias)
         raw = ops.conv2d(x, _phase_pack(unit, w, True), C, k, s, d, sc, sh, None, False)
-        bn = unit[1] if unit.has_bn else None
-        code = _relu_code(relu)
-        y, mean, invstd, scale, shift, batch_stats = _unit_bn_forward(bn, raw, gamma, beta, skip, code, C, x.device)
-        ctx.unit, ctx.code, ctx.batch_stats = unit, code, batch_stats
-        ctx.has = (bias is not None, gamma is not None, beta is not None, skip is not None)
-        ctx.save_for_backward(x, w, raw, y if code == 1 and skip is not None else None, scale, shift, mean, invstd)
-        return _carried_outputs(ctx, y, x_in, skip, carry_x, carry_skip)
+        return _unit_forward_tail(ctx, unit, raw, x, w, x_in, gamma, beta, bias, skip, relu, carry_x, carry_skip)
 
     @staticmethod
     def backward(ctx, *grads):
-        dy, dx_acc, dres_acc = _carried_grads(ctx, grads)
-        x, w, raw, y, scale, shift, mean, invstd = ctx.saved_tensors
-        unit, code = ctx.unit, ctx.code
+        unit = ctx.unit
         unit.__dict__["_dmb_pack_fwd"] = None     # any backward call ends the forward phase of the unit's packs (_phase_pack)
+        dc, dx_acc, x, w, bn_grads = _unit_backward_head(ctx, grads)
         k, s, d = unit.kernel_size, unit.stride, unit.dilation
-        has_bias, has_gamma, has_beta, has_skip = ctx.has
-        dy = torch.zeros_like(raw) if dy is None else dy.contiguous()
-        need_dres = has_skip and ctx.needs_input_grad[5]
-        if not need_dres:
-            dres_acc = None
-        dc, dgamma, dbeta, dres = ops.bn_act_bwd(dy, raw, y, scale, shift, mean, invstd, _mask_mode(code, has_skip), ctx.batch_stats,
-                                                 want_dres=need_dres and code == 1, dres_acc=dres_acc)
-        if need_dres and code != 1 and dres_acc is None:
-            dres = dy
-        dw = dx = dbias = None
+        dw = dx = None
         if ctx.needs_input_grad[1]:
             if k == 5:     # 5x5 stride 2 = 3x3 stride 1 on the space-to-depth input (GC-Net's first layer)
-                dw = _k3_as_k5s2_grad(ops.conv2d_wgrad(_space_to_depth(_even(x)).contiguous(), dc, 3, 1), x.shape[1])
+                dw = _k5s2_wgrad(x, dc)
             elif s == 1:
                 dw = ops.conv2d_wgrad(x, dc, k, d)
             elif k == 3:   # stride 2: the 3-D stride-2 weight gradient at depth 1, middle plane of its taps
@@ -680,7 +676,7 @@ class Conv2dUnitFn(torch.autograd.Function):
                 dw = ops.conv2d_wgrad(x[:, :, ::2, ::2].contiguous(), dc, 1, 1)
         if ctx.needs_input_grad[0]:
             if k == 5:
-                dx = _depth_to_space(ops.conv2d_dgrad(dc, _k5s2_as_k3(w)))[:, :, :x.shape[2], :x.shape[3]].contiguous()
+                dx = _k5s2_dgrad(dc, _k5s2_as_k3(w), x)
             elif s == 1:
                 dx = ops.conv2d_dgrad(dc, w, d, residual=dx_acc, packs=_phase_pack(unit, w, False))
                 dx_acc = None
@@ -691,28 +687,11 @@ class Conv2dUnitFn(torch.autograd.Function):
                 dx[:, :, ::2, ::2] = ops.conv2d_dgrad(dc, w, 1)
             if dx_acc is not None:   # the forms without a skip operand in their data-gradient launch
                 dx = dx + dx_acc
-        if has_bias and ctx.needs_input_grad[2]:
-            dbias = torch.zeros_like(dbeta) if ctx.batch_stats else scale * dbeta
-        return (dx, dw, dbias, dgamma if has_gamma and ctx.needs_input_grad[3] else None,
-                dbeta if has_beta and ctx.needs_input_grad[4] else None, dres if need_dres else None, None, None, None, None)
+        return _unit_backward_tail(ctx, dx, dw, bn_grads)
 
 
 def conv2d_unit(unit, x, residual=None, relu=False):
-    conv = unit[0]
-    bn = unit[1] if unit.has_bn else None
-    gamma = bn.weight if bn is not None and bn.affine else None
-    beta = bn.bias if bn is not None and bn.affine else None
-    reg, x, residual, cx, cs = _carry_plan(x, residual)
-    out = Conv2dUnitFn.apply(x, conv.weight, conv.bias, gamma, beta, residual, unit, relu, cx, cs)
-    if not (cx or cs):
-        return out
-    i = 1
-    if cx:
-        reg[id(x)] = (x, out[i])
-        i += 1
-    if cs:
-        reg[id(residual)] = (residual, out[i])
-    return out[0]
+    return _apply_carried(Conv2dUnitFn, unit, x, residual, relu)
 
 
 class BareConv1x1Fn(torch.autograd.Function):
@@ -765,6 +744,16 @@ def _k3_as_k5s2_grad(dw3, Ci):
     return dw3.view(Co, Ci, 2, 2, 3, 3).permute(0, 1, 4, 2, 5, 3).reshape(Co, Ci, 6, 6)[:, :, :5, :5].contiguous()
 
 
+def _k5s2_wgrad(x, dc):
+    """Weight gradient [Co, Ci, 5, 5] of a 5x5 stride-2 layer: that of the 3x3 layer on the space-to-depth input, folded back."""
+    return _k3_as_k5s2_grad(ops.conv2d_wgrad(_space_to_depth(_even(x)).contiguous(), dc, 3, 1), x.shape[1])
+
+
+def _k5s2_dgrad(dc, w3, x):
+    """Data gradient of a 5x5 stride-2 layer with the 3x3 weight ``w3 = _k5s2_as_k3(w)``, cut back to an odd-sized ``x``."""
+    return _depth_to_space(ops.conv2d_dgrad(dc, w3))[:, :, :x.shape[2], :x.shape[3]].contiguous()
+
+
 class BareConv2dFn(torch.autograd.Function):
     """A bare nn.Conv2d with bias (backbones/StereoNet.py:26-27,76: 5x5 stride 2 or 3x3 stride 1; edge_aware.py:42 with its skip
     add and ReLU): y = act(conv(x) + bias (+ skip)).  The 5x5 stride-2 layers take their gradients through the equivalent 3x3
@@ -799,14 +788,14 @@ class BareConv2dFn(torch.autograd.Function):
                                            want_dres=need_dres and ctx.relu)
         if need_dres and not ctx.relu:
             dres = dy
-        k, Ci = w.shape[2], w.shape[1]
+        k = w.shape[2]
         dx = dw = None
         if k == 5:
             w3 = _k5s2_as_k3(w)
             if ctx.needs_input_grad[1]:
-                dw = _k3_as_k5s2_grad(ops.conv2d_wgrad(_space_to_depth(_even(x)).contiguous(), dc, 3, 1), Ci)
+                dw = _k5s2_wgrad(x, dc)
             if ctx.needs_input_grad[0]:
-                dx = _depth_to_space(ops.conv2d_dgrad(dc, w3))[:, :, :x.shape[2], :x.shape[3]].contiguous()
+                dx = _k5s2_dgrad(dc, w3, x)
         else:
             if ctx.needs_input_grad[1]:
                 dw = ops.conv2d_wgrad(x, dc, k, 1)

@@ -306,27 +306,31 @@ def _hw_stride(stride, what):
     return stride
 
 
-def _conv3d_k3_hw(x, wpack, Co, scale, shift, residual, stride_hw, relu, out):
-    """conv3d_k3's launches on dmb_conv3d_k3_hw_f32 (ctypes only): stride (1, 2, 2), and stride 1 with 16 output channels."""
-    lib = _lib.load()
+def _pack_ok(wpack, need, Ci, Co, what):
+    if wpack.numel() != need:
+        raise _lib.DmbLibraryError("%s: packed weights hold %d floats, %d -> %d channels need %d" % (what, wpack.numel(), Ci, Co, need))
+
+
+def _unit_conv3d(fn, tag, what, x, wpack, scale, shift, residual, out, out_shape, need, dims, tail):
+    """The ctypes launch every 3-D unit convolution takes: ``fn(x, wpack, scale, shift, residual, y, *dims, *tail, stream)`` with
+    ``dims`` = (B, Ci, Co, D, H, W) of x, behind the operand checks and inside the kernel-timer bracket ``tag`` (None: no
+    bracket).  ``out_shape``: of y, the caller's ``out`` or a fresh tensor; ``need``: the floats ``wpack`` must hold; ``tail``:
+    the arguments between W and the stream, or a function that returns them and runs after the checks."""
     x = _f32c(x, "x")
-    B, Ci, D, H, W = x.shape
-    y = _out_tensor(out, (B, Co, D, (H - 1) // stride_hw + 1, (W - 1) // stride_hw + 1), x.device, "conv3d_k3")
+    y = _out_tensor(out, out_shape, x.device, what)
     if residual is not None and tuple(residual.shape) != tuple(y.shape):
         raise _lib.DmbLibraryError("residual shape %s != output shape %s" % (tuple(residual.shape), tuple(y.shape)))
-    _affine_ok(scale, shift, Co, "conv3d_k3")
-    if wpack.numel() != lib.dmb_conv3d_packed_floats(Co, Ci):
-        raise _lib.DmbLibraryError("conv3d_k3: packed weights hold %d floats, %d -> %d channels need %d"
-                                   % (wpack.numel(), Ci, Co, lib.dmb_conv3d_packed_floats(Co, Ci)))
-    tag = "conv3d_k3_s%s_%dto%d" % ("122" if stride_hw == 2 else "1", Ci, Co)
-    if _kernel_timer is not None:
-        _kernel_timer.start(tag)
-    check(lib.dmb_conv3d_k3_hw_f32(dev_ptr(x), dev_ptr(wpack), dev_ptr(scale, allow_none=True),
-                                   dev_ptr(shift, allow_none=True), dev_ptr(residual, allow_none=True), dev_ptr(y),
-                                   B, Ci, Co, D, H, W, stride_hw, _relu_mode(relu) | _conv_flags(), stream_ptr(x.device)),
-          "dmb_conv3d_k3_hw_f32")
-    if _kernel_timer is not None:
-        _kernel_timer.stop(tag)
+    _affine_ok(scale, shift, dims[2], what)
+    _pack_ok(wpack, need, dims[1], dims[2], what)
+    if callable(tail):
+        tail = tail()
+    timer = _kernel_timer if tag is not None else None
+    if timer is not None:
+        timer.start(tag)
+    check(fn(dev_ptr(x), dev_ptr(wpack), dev_ptr(scale, allow_none=True), dev_ptr(shift, allow_none=True),
+             dev_ptr(residual, allow_none=True), dev_ptr(y), *dims, *tail, stream_ptr(x.device)), fn.__name__)
+    if timer is not None:
+        timer.stop(tag)
     return y
 
 
@@ -334,7 +338,12 @@ def conv3d_k3(x, wpack, Co, scale=None, shift=None, residual=None, stride=1, rel
     """``stride``: 1, 2, or the tuple (1, 2, 2) ((1, 1, 1) and (2, 2, 2) mean 1 and 2)."""
     stride = _hw_stride(stride, "conv3d_k3")
     if stride == "hw" or (stride == 1 and Co == 16):
-        return _conv3d_k3_hw(x, wpack, Co, scale, shift, residual, 2 if stride == "hw" else 1, relu, out)
+        # dmb_conv3d_k3_hw_f32 (ctypes only): stride (1, 2, 2), and stride 1 with 16 output channels
+        lib, s = _lib.load(), 2 if stride == "hw" else 1
+        B, Ci, D, H, W = x.shape
+        return _unit_conv3d(lib.dmb_conv3d_k3_hw_f32, "conv3d_k3_s%s_%dto%d" % ("122" if s == 2 else "1", Ci, Co), "conv3d_k3",
+                            x, wpack, scale, shift, residual, out, (B, Co, D, (H - 1) // s + 1, (W - 1) // s + 1),
+                            lib.dmb_conv3d_packed_floats(Co, Ci), (B, Ci, Co, D, H, W), (s, _relu_mode(relu) | _conv_flags()))
     sh = _lib.shim()
     if sh is not None:      # the torch-extension shim: the same checks and the same C-ABI call, without the interpreter
         if _kernel_timer is not None:
@@ -345,25 +354,10 @@ def conv3d_k3(x, wpack, Co, scale=None, shift=None, residual=None, stride=1, rel
             _kernel_timer.stop("conv3d_k3_s%d_%dto%d" % (stride, x.shape[1], Co))
         return y
     lib = _lib.load()
-    x = _f32c(x, "x")
     B, Ci, D, H, W = x.shape
-    Do, Ho, Wo = (D - 1) // stride + 1, (H - 1) // stride + 1, (W - 1) // stride + 1
-    y = _out_tensor(out, (B, Co, Do, Ho, Wo), x.device, "conv3d_k3")
-    if residual is not None and tuple(residual.shape) != tuple(y.shape):
-        raise _lib.DmbLibraryError("residual shape %s != output shape %s" % (tuple(residual.shape), tuple(y.shape)))
-    _affine_ok(scale, shift, Co, "conv3d_k3")
-    if wpack.numel() != lib.dmb_conv3d_packed_floats(Co, Ci):
-        raise _lib.DmbLibraryError("conv3d_k3: packed weights hold %d floats, %d -> %d channels need %d"
-                                   % (wpack.numel(), Ci, Co, lib.dmb_conv3d_packed_floats(Co, Ci)))
-    tag = "conv3d_k3_s%d_%dto%d" % (stride, Ci, Co)
-    if _kernel_timer is not None:
-        _kernel_timer.start(tag)
-    check(lib.dmb_conv3d_k3_f32(dev_ptr(x), dev_ptr(wpack), dev_ptr(scale, allow_none=True),
-                                dev_ptr(shift, allow_none=True), dev_ptr(residual, allow_none=True), dev_ptr(y),
-                                B, Ci, Co, D, H, W, stride, _relu_mode(relu) | _conv_flags(), stream_ptr(x.device)), "dmb_conv3d_k3_f32")
-    if _kernel_timer is not None:
-        _kernel_timer.stop(tag)
-    return y
+    return _unit_conv3d(lib.dmb_conv3d_k3_f32, "conv3d_k3_s%d_%dto%d" % (stride, Ci, Co), "conv3d_k3", x, wpack, scale, shift,
+                        residual, out, (B, Co, (D - 1) // stride + 1, (H - 1) // stride + 1, (W - 1) // stride + 1),
+                        lib.dmb_conv3d_packed_floats(Co, Ci), (B, Ci, Co, D, H, W), (stride, _relu_mode(relu) | _conv_flags()))
 
 
 # ---------------------------------------------------------------------------------------------- first layer on a cat volume
@@ -696,20 +690,9 @@ def pack_conv3d_x6_weights(w):
 
 def conv3d_k3_x6(x, wpack, Co, scale=None, shift=None, residual=None, relu=False):
     lib = _lib.load()
-    x = _f32c(x, "x")
     B, Ci, D, H, W = x.shape
-    y = torch.empty((B, Co, D, H, W), dtype=torch.float32, device=x.device)
-    if residual is not None and tuple(residual.shape) != tuple(y.shape):
-        raise _lib.DmbLibraryError("residual shape %s != output shape %s" % (tuple(residual.shape), tuple(y.shape)))
-    tag = "conv3d_k3_s1_%dto%d" % (Ci, Co)
-    if _kernel_timer is not None:
-        _kernel_timer.start(tag)
-    check(lib.dmb_conv3d_k3_x6_f32(dev_ptr(x), dev_ptr(wpack), dev_ptr(scale, allow_none=True),
-                                   dev_ptr(shift, allow_none=True), dev_ptr(residual, allow_none=True), dev_ptr(y),
-                                   B, Ci, Co, D, H, W, _relu_mode(relu), stream_ptr(x.device)), "dmb_conv3d_k3_x6_f32")
-    if _kernel_timer is not None:
-        _kernel_timer.stop(tag)
-    return y
+    return _unit_conv3d(lib.dmb_conv3d_k3_x6_f32, "conv3d_k3_s1_%dto%d" % (Ci, Co), "conv3d_k3_x6", x, wpack, scale, shift, residual,
+                        None, (B, Co, D, H, W), lib.dmb_conv3d_x6_packed_bytes(Co, Ci) // 4, (B, Ci, Co, D, H, W), (_relu_mode(relu),))
 
 
 def conv3d_k3_c1(x, w, bias=0.0, residual=None):
@@ -750,30 +733,6 @@ def deconv3d_workspace(device):
     return ws
 
 
-def _deconv3d_k3_hw(x, wpack, Co, scale, shift, residual, relu, out):
-    """deconv3d_k3s2's launch on dmb_deconv3d_k3_hw_f32 (ctypes only): stride (1, 2, 2), output_padding (0, 1, 1)."""
-    lib = _lib.load()
-    x = _f32c(x, "x")
-    B, Ci, D, H, W = x.shape
-    y = _out_tensor(out, (B, Co, D, 2 * H, 2 * W), x.device, "deconv3d_k3s2")
-    if residual is not None and tuple(residual.shape) != tuple(y.shape):
-        raise _lib.DmbLibraryError("residual shape %s != output shape %s" % (tuple(residual.shape), tuple(y.shape)))
-    _affine_ok(scale, shift, Co, "deconv3d_k3s2")
-    if wpack.numel() != lib.dmb_deconv3d_packed_floats(Ci, Co):
-        raise _lib.DmbLibraryError("deconv3d_k3s2: packed weights hold %d floats, %d -> %d channels need %d"
-                                   % (wpack.numel(), Ci, Co, lib.dmb_deconv3d_packed_floats(Ci, Co)))
-    tag = "deconv3d_k3_s122_%dto%d" % (Ci, Co)
-    if _kernel_timer is not None:
-        _kernel_timer.start(tag)
-    check(lib.dmb_deconv3d_k3_hw_f32(dev_ptr(x), dev_ptr(wpack), dev_ptr(scale, allow_none=True),
-                                     dev_ptr(shift, allow_none=True), dev_ptr(residual, allow_none=True), dev_ptr(y),
-                                     B, Ci, Co, D, H, W, _relu_mode(relu) | _conv_flags(), stream_ptr(x.device)),
-          "dmb_deconv3d_k3_hw_f32")
-    if _kernel_timer is not None:
-        _kernel_timer.stop(tag)
-    return y
-
-
 def deconv3d_k3s2(x, wpack, Co, scale=None, shift=None, residual=None, relu=False, workspace="auto", out=None, out_width=None,
                   stride=(2, 2, 2)):
     """``workspace``: "auto" = the per-stream workspace above; None = the kernel form without counters; or an int32 tensor of
@@ -784,7 +743,11 @@ def deconv3d_k3s2(x, wpack, Co, scale=None, shift=None, residual=None, relu=Fals
     if stride == (1, 2, 2):
         if not (isinstance(workspace, str) and workspace == "auto") or out_width is not None:
             raise _lib.DmbLibraryError("deconv3d_k3s2: stride (1, 2, 2) takes no workspace and no out_width")
-        return _deconv3d_k3_hw(x, wpack, Co, scale, shift, residual, relu, out)
+        lib = _lib.load()            # dmb_deconv3d_k3_hw_f32 (ctypes only): output_padding (0, 1, 1)
+        B, Ci, D, H, W = x.shape
+        return _unit_conv3d(lib.dmb_deconv3d_k3_hw_f32, "deconv3d_k3_s122_%dto%d" % (Ci, Co), "deconv3d_k3s2", x, wpack, scale, shift,
+                            residual, out, (B, Co, D, 2 * H, 2 * W), lib.dmb_deconv3d_packed_floats(Ci, Co), (B, Ci, Co, D, H, W),
+                            (_relu_mode(relu) | _conv_flags(),))
     if stride != (2, 2, 2):
         raise _lib.DmbLibraryError("deconv3d_k3s2: stride %s is not built: (2, 2, 2) or (1, 2, 2)" % (stride,))
     sh = _lib.shim()
@@ -794,27 +757,18 @@ def deconv3d_k3s2(x, wpack, Co, scale=None, shift=None, residual=None, relu=Fals
         return sh.deconv3d_k3s2(x if x.is_contiguous() else x.contiguous(), wpack, Co, scale, shift, residual,
                                 _relu_mode(relu) | _conv_flags(), workspace, out, -1 if out_width is None else int(out_width))
     lib = _lib.load()
-    x = _f32c(x, "x")
     B, Ci, D, H, W = x.shape
     Wout = 2 * W if out_width is None else int(out_width)
-    y = _out_tensor(out, (B, Co, 2 * D, 2 * H, Wout), x.device, "deconv3d_k3s2")
-    if residual is not None and tuple(residual.shape) != tuple(y.shape):
-        raise _lib.DmbLibraryError("residual shape %s != output shape %s" % (tuple(residual.shape), tuple(y.shape)))
-    _affine_ok(scale, shift, Co, "deconv3d_k3s2")
-    if wpack.numel() != lib.dmb_deconv3d_packed_floats(Ci, Co):
-        raise _lib.DmbLibraryError("deconv3d_k3s2: packed weights hold %d floats, %d -> %d channels need %d"
-                                   % (wpack.numel(), Ci, Co, lib.dmb_deconv3d_packed_floats(Ci, Co)))
-    if isinstance(workspace, str):
-        workspace = deconv3d_workspace(x.device)
-    if workspace is not None and (workspace.dtype != torch.int32 or workspace.numel() * 4 < _lib.DECONV3D_WORKSPACE_BYTES
-                                  or workspace.device != x.device or not workspace.is_contiguous()):
-        raise _lib.DmbLibraryError("deconv3d_k3s2: workspace must be a contiguous int32 tensor of %d bytes on %s"
-                                   % (_lib.DECONV3D_WORKSPACE_BYTES, x.device))
-    check(lib.dmb_deconv3d_k3s2_f32(dev_ptr(x), dev_ptr(wpack), dev_ptr(scale, allow_none=True),
-                                    dev_ptr(shift, allow_none=True), dev_ptr(residual, allow_none=True), dev_ptr(y),
-                                    B, Ci, Co, D, H, W, Wout, _relu_mode(relu) | _conv_flags(),
-                                    None if workspace is None else ctypes.c_void_p(workspace.data_ptr()), stream_ptr(x.device)), "dmb_deconv3d_k3s2_f32")
-    return y
+
+    def tail():     # after the operand checks and the output: the workspace is the last thing this call may allocate
+        ws = deconv3d_workspace(x.device) if isinstance(workspace, str) else workspace
+        if ws is not None and (ws.dtype != torch.int32 or ws.numel() * 4 < _lib.DECONV3D_WORKSPACE_BYTES
+                               or ws.device != x.device or not ws.is_contiguous()):
+            raise _lib.DmbLibraryError("deconv3d_k3s2: workspace must be a contiguous int32 tensor of %d bytes on %s"
+                                       % (_lib.DECONV3D_WORKSPACE_BYTES, x.device))
+        return Wout, _relu_mode(relu) | _conv_flags(), None if ws is None else ctypes.c_void_p(ws.data_ptr())
+    return _unit_conv3d(lib.dmb_deconv3d_k3s2_f32, None, "deconv3d_k3s2", x, wpack, scale, shift, residual, out,
+                        (B, Co, 2 * D, 2 * H, Wout), lib.dmb_deconv3d_packed_floats(Ci, Co), (B, Ci, Co, D, H, W), tail)
 
 
 # ---------------------------------------------------------------------------------------------- conv backward
@@ -1076,9 +1030,7 @@ def conv3d_k3_bnstats(x, wpack, Co):
     P = int(lib.dmb_conv3d_k3_bnstats_partials(B, Ci, Co, D, H, W))
     if P <= 0 or x.data_ptr() % 16:
         return None
-    if wpack.numel() != lib.dmb_conv3d_packed_floats(Co, Ci):
-        raise _lib.DmbLibraryError("conv3d_k3_bnstats: packed weights hold %d floats, %d -> %d channels need %d"
-                                   % (wpack.numel(), Ci, Co, lib.dmb_conv3d_packed_floats(Co, Ci)))
+    _pack_ok(wpack, lib.dmb_conv3d_packed_floats(Co, Ci), Ci, Co, "conv3d_k3_bnstats")
     raw = torch.empty((B, Co, D, H, W), dtype=torch.float32, device=x.device)
     parts = torch.empty((Co, P, 2), dtype=torch.float64, device=x.device)
     check(lib.dmb_conv3d_k3_bnstats_f32(dev_ptr(x), dev_ptr(wpack), dev_ptr(raw), dev_ptr(parts), B, Ci, Co, D, H, W, stream_ptr(x.device)),
