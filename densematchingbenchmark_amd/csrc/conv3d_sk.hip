@@ -21,9 +21,9 @@
 // in the last bits (and with them batch 1 from batch 4 where this form is picked) -- both are FP32 evaluations of the same
 // convolution; the tests bound them against the FP64 yardstick instead of against each other.
 //
-// Which launches take this form is a cost estimate in dmb_conv3d_k3_f32 (conv3d.hip) and dmb_deconv3d_k3s2_f32 (deconv3d.hip); conv3d_sk_try returns -1 where the shape
+// Which launches take this form is a cost estimate in dmb_conv3d_k3_f32 (conv3d.hip) and deconv_plan (deconv3d_plan.h); conv3d_sk_try returns -1 where the shape
 // does not qualify.
-#include "dmb_common.h"
+#include "deconv3d_plan.h"
 
 namespace dmb {
 
@@ -568,15 +568,13 @@ __global__ __launch_bounds__(C::NTHREADS) void deconv3d_sk_kernel(const float* _
     deconv_sk_body<C, 0, 0>(lds, x, wp, scale, shift, res, y, gm, (wg - g3) / NTT, (G - g3) / NTT, (wg - g3) % NTT);
 }
 
+// (deconv_plan, deconv3d_plan.h, has checked what this form requires: the grid and the LDS buffer fit)
 template <class C>
-static int launch_dsk(const float* x, const float* wp, const float* scale, const float* shift, const float* res, float* y, int B,
-                      int Ci, int Co, int D, int H, int W, int Wout, int relu, hipStream_t st) {
-  const int ntx = cdiv(W, C::TXI), nty = cdiv(H, C::TYI), NTT = cdiv(Co, 32);
-  const long long ntiles = (long long)B * D * nty * ntx;
-  if (ntiles * 4 * NTT > 0x7fffffffLL) return fail(DMB_EUNSUPPORTED, "deconv3d: grid too large");
-  const size_t in_floats = (size_t)Ci * C::IN_MAX, part_floats = (size_t)C::NW * C::PART;
+static int launch_dsk(const DeconvArgs& a) {
+  const int ntx = cdiv(a.W, C::TXI), nty = cdiv(a.H, C::TYI), NTT = cdiv(a.Co, 32);
+  const long long ntiles = (long long)a.B * a.D * nty * ntx;
+  const size_t in_floats = (size_t)a.Ci * C::IN_MAX, part_floats = (size_t)C::NW * C::PART;
   const size_t buf_floats = in_floats > part_floats ? in_floats : part_floats;
-  if (buf_floats * sizeof(float) > 160 * 1024) return -1;
   // with at most two single-buffered workgroups per CU's worth of items every workgroup takes ONE tile; beyond that the walk is
   // persistent on the chip's workgroup slots: two per CU where two double-buffered workgroups fit the LDS, else one
   const int two_bufs = 2 * buf_floats * sizeof(float) <= 160 * 1024;
@@ -596,31 +594,17 @@ static int launch_dsk(const float* x, const float* wp, const float* scale, const
     }
     nbuf = two_bufs ? 2 : 1;
   }
-  DSKGeom gm = {Ci, D, H, W, Wout, ntx, nty, NTT, Co, relu, (int)ntiles, (int)buf_floats, nbuf};
+  DSKGeom gm = {a.Ci, a.D, a.H, a.W, a.Wout, ntx, nty, NTT, a.Co, a.relu & 0xff, (int)ntiles, (int)buf_floats, nbuf};
   const size_t lds = nbuf * buf_floats * sizeof(float);
   DMB_ENSURE_LDS((&deconv3d_sk_kernel<C>), (size_t)(160 * 1024));
-  hipLaunchKernelGGL((deconv3d_sk_kernel<C>), dim3((unsigned)(gc[0] + gc[1] + gc[2] + gc[3])), dim3(C::NTHREADS), lds, st, x, wp, scale, shift,
-                     res, y, gm, (int)gc[0], (int)(gc[0] + gc[1]), (int)(gc[0] + gc[1] + gc[2]));
+  hipLaunchKernelGGL((deconv3d_sk_kernel<C>), dim3((unsigned)(gc[0] + gc[1] + gc[2] + gc[3])), dim3(C::NTHREADS), lds, a.st, a.x, a.wp, a.scale,
+                     a.shift, a.res, a.y, gm, (int)gc[0], (int)(gc[0] + gc[1]), (int)(gc[0] + gc[1] + gc[2]));
   return launch_status("deconv3d split-K launch failed");
 }
 
-// variant: 1 = 16 x 2 input positions per workgroup, eight waves; 2 = 32 x 2, eight waves; 3 = 16 x 2, four waves; 4 = 32 x 2, four waves.
-// -1: the shape does not qualify.
-int deconv3d_sk_try(int variant, const float* x, const float* wp, const float* scale, const float* shift, const float* res, float* y,
-                    int B, int Ci, int Co, int D, int H, int W, int Wout, int relu, hipStream_t st) {
-  if (Co > 64 || W % 4 != 0 || Wout % 4 != 0 || ((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)res)) & 15) != 0) return -1;
-  const int nw = variant <= 2 ? 8 : 4;
-  if (Ci % (2 * nw) != 0 || Ci / (2 * nw) > 4 * (variant <= 2 ? 1 : 2)) return -1;
-  if ((long long)(Ci / nw) * D * H * W * 4 >= 0x7fffffffLL) return -1;
-  switch (variant) {   // (dsk_variant picks 3 only: the others lost every measured shape and exist in the development build)
-    case 3: return launch_dsk<DSKCfg<4, 1, 8>>(x, wp, scale, shift, res, y, B, Ci, Co, D, H, W, Wout, relu, st);
-#ifdef DMB_DEV
-    case 1: return launch_dsk<DSKCfg<8, 1, 4>>(x, wp, scale, shift, res, y, B, Ci, Co, D, H, W, Wout, relu, st);
-    case 2: return launch_dsk<DSKCfg<8, 2, 4>>(x, wp, scale, shift, res, y, B, Ci, Co, D, H, W, Wout, relu, st);
-    case 4: return launch_dsk<DSKCfg<4, 2, 8>>(x, wp, scale, shift, res, y, B, Ci, Co, D, H, W, Wout, relu, st);
-#endif
-  }
-  return -1;
-}
+// the one split-K tile of the transposed convolution (deconv3d_plan.h, which restates what the plan needs of it)
+using DSKTile = DSKCfg<DSK_NW, DSK_XS, 8>;
+static_assert(DSKTile::TXI == DSK_TXI && DSKTile::TYI == DSK_TYI && DSKTile::IN_MAX == DSK_IN_MAX && DSKTile::PART == DSK_PART, "deconv3d_plan.h");
+int deconv3d_sk_launch(int, const DeconvArgs& a) { return launch_dsk<DSKTile>(a); }
 
 }  // namespace dmb

@@ -1,9 +1,10 @@
 // Transposed 3x3x3 convolution (stride 2) of the cost aggregators, box-tiled persistent form: the FP32-MFMA implicit GEMM described
-// at the head of conv3d.hip, one accumulator set per output parity.  dmb_deconv3d_k3s2_f32 tries the split-K form (conv3d_sk.hip) and
-// the work-queue form (deconv3d_zy.hip) first.
+// at the head of conv3d.hip, one accumulator set per output parity.  dmb_deconv3d_k3s2_f32 (at the end) runs what deconv_plan
+// (deconv3d_plan.h) names: the split-K form (conv3d_sk.hip), the work-queue form (deconv3d_zy.hip) or this one.
 #include <type_traits>
 
 #include "conv3d_mfma.h"
+#include "deconv3d_plan.h"
 
 #ifndef DMB_EPI_LD
 #define DMB_EPI_LD 0   // buffer cache policy of the transposed kernel's epilogue: bit 1 = nt (streaming)
@@ -432,12 +433,11 @@ __global__ __launch_bounds__(256, C::WPE) void deconv3d_kernel(const float* __re
                       ntiles, relu, cvalid);
 }
 
+// (deconv_plan has checked that the tile count fits the grid)
 template <class C>
-static int launch_deconv(const float* x, const float* wp, const float* scale, const float* shift, const float* res,
-                         float* y, int B, int Ci, int Co, int D, int H, int W, int relu, hipStream_t st) {
-  const int ntx = cdiv(W, C::TX), nty = cdiv(H, C::TY), ntz = cdiv(D, C::TZ);
-  const long long ntiles = (long long)B * ntx * nty * ntz;
-  if (ntiles > 0x3fffffffLL) return fail(DMB_EUNSUPPORTED, "deconv3d: grid too large");
+static int launch_deconv(const DeconvArgs& a) {
+  const int ntx = cdiv(a.W, C::TX), nty = cdiv(a.H, C::TY), ntz = cdiv(a.D, C::TZ);
+  const long long ntiles = (long long)a.B * ntx * nty * ntz;
   const size_t lds = (size_t)(C::LDS_FLOATS + C::AFF_FLOATS + C::SCR_FLOATS) * sizeof(float);
   DMB_ENSURE_LDS((&deconv3d_kernel<C>), (size_t)(lds));
   const int ncu = num_cus();
@@ -456,68 +456,46 @@ static int launch_deconv(const float* x, const float* wp, const float* scale, co
     if (g0 > ntiles) g0 = ntiles;
     if (g1 > ntiles) g1 = ntiles;
   }
-  hipLaunchKernelGGL((deconv3d_kernel<C>), dim3((unsigned)(g0 + g1)), dim3(256), lds, st, x, wp, scale, shift, res, y, Ci,
-                     D, H, W, ntx, nty, ntz, (int)ntiles, (int)g0, relu, Co);
+  hipLaunchKernelGGL((deconv3d_kernel<C>), dim3((unsigned)(g0 + g1)), dim3(256), lds, a.st, a.x, a.wp, a.scale, a.shift, a.res, a.y,
+                     a.Ci, a.D, a.H, a.W, ntx, nty, ntz, (int)ntiles, (int)g0, a.relu, a.Co);
   return launch_status("deconv3d launch failed");
 }
+
+// The two-parity tile of plan config K (deconv3d_plan.h: D_TILE; 32-row tiles first).  Fewer than 32 output channels (GC-Net's
+// 1-channel head) run the 32-row tiles: zero-padded weight rows, masked scalar epilogue.
+template <int K, int T = K % D_TILES, int CO = K < D_TILES ? 32 : 64>
+using DTileCfg = DCfg<0, CO, D_TILE[T].ty, D_TILE[T].tx, 256 / CO, CO / 32, D_TILE[T].v16, D_TILE[T].vepi>;
 
 }  // namespace dmb
 
 using namespace dmb;
 
-// Split-K form of the transposed convolution (csrc/conv3d_sk.hip): 0 = no, else its variant.  Units: input-resolution tiles.
-static int dsk_variant(int B, int Ci, int Co, int D, int H, int W) {
-  const long long tiles = (long long)B * D * cdiv(H, 2) * cdiv(W, 16);
-  const int ncu = num_cus();
-  // measured (profiles/r06_sk_probe_deconv.log, persistent form, four waves per workgroup; units = tiles x row tiles):
-  // 128 units ([1, 64, 4, 16, 32] -> 64 channels) 37.3 -> 14.2 us, 192 units 38.0 -> 16.7, 360 units 37.8 -> 26.7, 576 units 59.3 -> 40.3,
-  // 1632 units 99 against 103 (a tie); 512 units ([1, 64, 8, 32, 64] -> 32 channels) 50.2 -> 36.9, 768 units 69.2 -> 52.5, 1200 units
-  // 80.6 -> 76.6, 2304 units 136 against 143: from there on the work-queue kernel (deconv3d_zy.hip) wins
-  const long long units = tiles * cdiv(Co, 32);
-  if (Ci % 8 == 0 && Ci <= 64 && units <= 5LL * ncu) return 3;   // 16 x 2 input positions per workgroup, four waves
-  return 0;
+static int align_of(const void* p) {   // a pointer enters the plan as its alignment: 1 .. 16 bytes (NULL: 16)
+  const uintptr_t low = (uintptr_t)p & 15;
+  return low ? (int)(low & (~low + 1)) : 16;
+}
+
+extern "C" int dmb_deconv3d_k3s2_plan(int B, int Ci, int Co, int D, int H, int W, int Wout, int x_align, int y_align, int residual_align,
+                                      int workspace_align, int single_chain, int ncu) {
+  const char* why = "";
+  const int plan = deconv_plan({B, Ci, Co, D, H, W, Wout, x_align, y_align, residual_align, workspace_align, single_chain != 0,
+                                ncu > 0 ? ncu : num_cus()}, &why);
+  set_last_error(why);
+  return plan;
 }
 
 extern "C" int dmb_deconv3d_k3s2_f32(const float* x, const float* wpack, const float* scale, const float* shift,
                                      const float* residual, float* y, int B, int Ci, int Co, int D, int H, int W, int Wout,
                                      int relu, void* workspace, void* stream) {
-  if (!x || !wpack || !y || B <= 0 || Ci <= 0 || D <= 0 || H <= 0 || W <= 0) return fail(DMB_EINVAL, "deconv3d: bad argument");
-  if (Wout <= 0 || Wout > 2 * W || Wout <= 2 * W - 8 || (Wout & 1)) return fail(DMB_EINVAL, "deconv3d: Wout must be 2 W, or 2 W minus the (at most 3) doubled padding columns");
-  if ((long long)8 * D * H * W * 4 >= 0x7fffffffLL)
-    return fail(DMB_EUNSUPPORTED, "deconv3d: 8 input channels of one batch item must stay below 2 GiB (32-bit buffer offsets)");
-  hipStream_t st = (hipStream_t)stream;
-  const bool single_chain = (relu & DMB_CONV_SINGLE_CHAIN) != 0;
-  relu &= 0xff;
-  relu |= DMB_OPT(6) << 8;   // (development build: diagnostics)
-  {
-    // (round 6) launches that leave most of the chip idle: split-K over the waves of a workgroup (csrc/conv3d_sk.hip).
-    // DMB_OPT(25) (development build): 1 = never, k >= 2 = force variant k - 1.
-    int v = single_chain ? 0 : dsk_variant(B, Ci, Co, D, H, W);
-    if (DMB_OPT(25) == 1) v = 0;
-    if (DMB_OPT(25) >= 2) v = DMB_OPT(25) - 1;
-    if (v > 0) {
-      const int rc = deconv3d_sk_try(v, x, wpack, scale, shift, residual, y, B, Ci, Co, D, H, W, Wout, relu & 0xff, st);
-      if (rc != -1) return rc;
-    }
-  }
-  if (workspace && !DMB_OPT(3) && !DMB_OPT(7)) {   // three workgroups per CU where the shape admits it (csrc/deconv3d_zy.hip)
-    const int rc = deconv3d_zy_try(x, wpack, scale, shift, residual, y, B, Ci, Co, D, H, W, Wout, relu, static_cast<int*>(workspace), st);
-    if (rc != -1) return rc;
-  }
-  if (Wout != 2 * W) return fail(DMB_EUNSUPPORTED, "deconv3d: a row-padded input (Wout < 2 W) needs the workspace form: Co 32 or 64, Ci % 16 == 0, Wout % 4 == 0, aligned operands");
-  const bool v16 = W % 4 == 0 && ((uintptr_t)x & 15) == 0 && !DMB_OPT(3);   // 16-byte aligned rows
-  // 16-byte epilogue: aligned output / residual rows, every channel real, one batch item of the output below 2 GiB
-  const bool vepi = v16 && Co % 32 == 0 && ((((uintptr_t)y | (uintptr_t)residual) & 15) == 0) &&
-                    (long long)Co * 8 * D * H * W * 4 < 0x7fffffffLL && !DMB_OPT(7);
-  // 2 rows x 28 columns per item instead of 1 x 60 where that computes fewer positions (input W = 64: 3 x 32 against
-  // 2 x 64 per row; the tile width stays a multiple of 4 for the 16-byte staging)
-  const bool narrow = v16 && cdiv(W, 28) * 32 < cdiv(W, 60) * 64;
-#define DMB_DC(CO, TY, TX, CK, WN, V, E) launch_deconv<DCfg<0, CO, TY, TX, CK, WN, V, E>>(x, wpack, scale, shift, residual, y, B, Ci, Co, D, H, W, relu, st)
-  if (Co == 64 && narrow) return vepi ? DMB_DC(64, 2, 28, 4, 2, true, true) : DMB_DC(64, 2, 28, 4, 2, true, false);
-  if (Co <= 32 && narrow) return vepi ? DMB_DC(32, 2, 28, 8, 1, true, true) : DMB_DC(32, 2, 28, 8, 1, true, false);
-  if (Co == 64) return !v16 ? DMB_DC(64, 1, 60, 4, 2, false, false) : (vepi ? DMB_DC(64, 1, 60, 4, 2, true, true) : DMB_DC(64, 1, 60, 4, 2, true, false));
-  if (Co <= 32)   // fewer than 32 channels (GC-Net's 1-channel head): zero-padded weight rows, masked scalar epilogue
-    return !v16 ? DMB_DC(32, 1, 60, 8, 1, false, false) : (vepi ? DMB_DC(32, 1, 60, 8, 1, true, true) : DMB_DC(32, 1, 60, 8, 1, true, false));
-#undef DMB_DC
-  return fail(DMB_EUNSUPPORTED, "deconv3d: output channels must be <= 32 or 64");
+  if (!x || !wpack || !y) return fail(DMB_EINVAL, "deconv3d: bad argument");
+  const char* why = "";
+  const int plan = deconv_plan({B, Ci, Co, D, H, W, Wout, align_of(x), align_of(y), align_of(residual), workspace ? align_of(workspace) : 0,
+                                (relu & DMB_CONV_SINGLE_CHAIN) != 0, num_cus()}, &why);
+  if (plan < 0) return fail(-plan, why);
+  const int cfg = plan & 0xff;
+  // bits 8..: the development build's diagnostic bits (option 6), passed on to the kernels
+  const DeconvArgs a{x, wpack, scale, shift, residual, y, B, Ci, Co, D, H, W, Wout, (relu & 0xff) | (DMB_OPT(6) << 8), (hipStream_t)stream};
+  if (plan >> 8 == DECONV_SPLIT_K) return deconv3d_sk_launch(cfg, a);
+  if (plan >> 8 == DECONV_QUEUE) return deconv3d_zy_launch(cfg, a, static_cast<int*>(workspace));
+  return deconv_visit(cfg, [&](auto k) { return launch_deconv<DTileCfg<decltype(k)::value>>(a); }, std::make_integer_sequence<int, 2 * D_TILES>{});
 }

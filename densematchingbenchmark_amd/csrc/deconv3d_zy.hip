@@ -37,7 +37,7 @@
 // other two forms: bit-identical results.
 #include <type_traits>
 
-#include "dmb_common.h"
+#include "deconv3d_plan.h"
 
 // Cache policy of the epilogue's stores / skip-operand loads (the aux operand of the buffer instructions on gfx950: 1 = sc0,
 // 2 = nt, 16 = sc1; build-time knobs, build.py: DMB_BUILD_DEFS).  The output is 8x the input and is not read again by this
@@ -55,7 +55,7 @@ namespace dmb {
 
 // MT_: 32-column MFMA tiles per input row of a work item: 2 (60 real positions + the halo column of the odd outputs in 64 staged
 // columns) or 1 (28 real positions in 32) -- the narrower tile computes fewer discarded columns where the image width is
-// awkward for 60 (80 columns: 3 x 32 computed instead of 2 x 64); deconv3d_zy_try picks per launch.
+// awkward for 60 (80 columns: 3 x 32 computed instead of 2 x 64); deconv_plan (deconv3d_plan.h) picks per launch.
 // FULL_ (round 6): all 32 MT positions of a staged row are real -- the row is staged 4 columns longer (pitch 32 MT + 4) instead of the
 // tile being 4 positions narrower than what the matrix cores compute.  For widths that are multiples of 32 (the training crops: 64
 // and 32 input columns) nothing computed is discarded, where the 28- / 60-column tiles compute 96 for 64 and 64 for 32.
@@ -115,7 +115,6 @@ struct ZYArgs {
   int lrun;      // log2 of the tiles per group of the item order
   int nparts;    // tile ranges in use (ZY_PARTS; 1 in the development build's single-list mode)
   int q, r;      // ntiles = q * nparts + r: range k holds q + (k < r) tiles from k q + min(k, r)
-  int stagger;   // development build: start-up delay unit (see the kernel)
 };
 
 // ---- drawing work items ---------------------------------------------------------------------------------------------------
@@ -428,8 +427,8 @@ __device__ __forceinline__ int zy_body(float* lds, int* slot, const ZYArgs& a, i
             // The uniform part goes into the VECTOR offset for stores (one v_add each), not into the scalar-offset operand:
             // with an SGPR soffset the compiler's hazard model lets the next VALU instruction overwrite the store's data
             // registers at once, and on this chip a 16-byte store still reads the data of its last lanes then -- under load
-            // (three workgroups per CU) lanes 12..15 of each 16 stored the NEXT pass's accumulator values (found with
-            // scripts/attic/zy_debug.py: one wrong float in 10^3, only with more than one workgroup per CU).  With a literal
+            // (three workgroups per CU) lanes 12..15 of each 16 stored the NEXT pass's accumulator values (profiles/r03_store_hazard.log:
+            // one wrong float in 10^3, only with more than one workgroup per CU).  With a literal
             // soffset the compiler inserts the wait states itself.
             __builtin_amdgcn_raw_buffer_store_b128(o, yrs, (int)(voff[mt] + soff(t, k)), 0, DMB_ZY_ST);
           }
@@ -460,13 +459,6 @@ __global__ __launch_bounds__(256, 3) void deconv3d_zy_kernel(ZYArgs a, const flo
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* aff = lds + 2 * C::BUF_MAX;
   __shared__ int slot[1];   // the next item, published by thread 0
-#ifdef DMB_DEV
-  // (development option 12) a start-up delay of (workgroup index mod 16) x stagger x 3.4 us: measured, no gain
-  if (a.stagger > 0) {
-    const int n = (int)((blockIdx.x * 7u) & 15u) * a.stagger;
-    for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(127);
-  }
-#endif
   // per-channel affine, staged once (LDS reads count on lgkmcnt and cost no registers across the item loop; see
   // deconv3d_kernel)
   if (threadIdx.x < C::COUT) {
@@ -503,71 +495,36 @@ __global__ __launch_bounds__(256, 3) void deconv3d_zy_kernel(ZYArgs a, const flo
   }
 }
 
+// (deconv_plan has checked that the items fit the grid and the ticket field of a published draw)
 template <class C>
-static int launch_zy(const float* x, const float* wp, const float* scale, const float* shift, const float* res, float* y,
-                     int B, int Ci, int D, int H, int W, int Wout, int relu, int* ws, hipStream_t st) {
-  const int ntx = cdiv(W, C::TX), nty = H, ntz = cdiv(D, C::TZ);
-  const long long ntiles = (long long)B * ntx * nty * ntz;
-  if (4 * ntiles > 0x3fffffffLL) return fail(DMB_EUNSUPPORTED, "deconv3d: grid too large");
+static int launch_zy(const DeconvArgs& d, int* ws) {
+  const int ntx = cdiv(d.W, C::TX), nty = d.H, ntz = cdiv(d.D, C::TZ);
+  const long long ntiles = (long long)d.B * ntx * nty * ntz;
   const size_t lds = (size_t)C::LDS_FLOATS * sizeof(float);
   DMB_ENSURE_LDS((&deconv3d_zy_kernel<C>), lds);
-  const long long slots = 3LL * num_cus() * (DMB_OPT(8) > 0 ? DMB_OPT(8) : 1);
-  long long grid = 4 * ntiles < slots ? 4 * ntiles : slots;
-  if (DMB_OPT(9) > 0 && DMB_OPT(9) < grid) grid = DMB_OPT(9);   // development: few workgroups walk many items
-  if (4 * ntiles >= (1LL << 27)) return -1;   // (ticket field of the published draw; 33 M tiles: far beyond any volume here)
-  const bool sel = DMB_OPT(21) == 0 || DMB_OPT(21) == C::COUT;   // (development option 21: options 16 / 20 for one width only)
-  int lrun = sel && DMB_OPT(16) > 0 ? DMB_OPT(16) - 1 : ZY_RUN_LOG2;   // (development option 16 = log2(tiles per group) + 1)
+  const long long slots = 3LL * num_cus();
+  const long long grid = 4 * ntiles < slots ? 4 * ntiles : slots;
+  int lrun = DMB_OPT(16) > 0 ? DMB_OPT(16) - 1 : ZY_RUN_LOG2;   // (development option 16 = log2(tiles per group) + 1)
   int nparts = ZY_PARTS;
-  if (sel && DMB_OPT(20)) {   // development: ONE class-major list over the whole layer (the round-3 order)
+  if (DMB_OPT(20)) {   // development: ONE class-major list over the whole layer (the round-3 order)
     nparts = 1;
     lrun = 0;
     while ((1LL << lrun) < ntiles) ++lrun;
   }
-  ZYArgs a{x, wp, res, y, ws, Ci, D, H, W, ntx, nty, ntz, (int)ntiles, relu & 0xff, relu >> 8, Wout, lrun, nparts,
-           (int)(ntiles / nparts), (int)(ntiles % nparts), DMB_OPT(12)};
-  hipLaunchKernelGGL((deconv3d_zy_kernel<C>), dim3((unsigned)grid), dim3(256), lds, st, a, scale, shift);
+  ZYArgs a{d.x, d.wp, d.res, d.y, ws, d.Ci, d.D, d.H, d.W, ntx, nty, ntz, (int)ntiles, d.relu & 0xff, d.relu >> 8, d.Wout, lrun, nparts,
+           (int)(ntiles / nparts), (int)(ntiles % nparts)};
+  hipLaunchKernelGGL((deconv3d_zy_kernel<C>), dim3((unsigned)grid), dim3(256), lds, d.st, a, d.scale, d.shift);
   return launch_status("deconv3d (z/y-parity items) launch failed");
 }
 
-// Entry for dmb_deconv3d_k3s2_f32 (deconv3d.hip): returns -1 when this form does not apply (the caller falls back to
-// deconv3d_kernel), otherwise the launch status.  Requirements: 16-byte aligned rows (W % 4 == 0, aligned bases), all 32 or
-// 64 output channels real, whole 16-channel chunks and at least two of them, 16 input channels of one batch item and one batch item of the output
-// below 2 GiB (32-bit buffer offsets).
-int deconv3d_zy_try(const float* x, const float* wp, const float* scale, const float* shift, const float* res, float* y,
-                    int B, int Ci, int Co, int D, int H, int W, int Wout, int relu, int* ws, hipStream_t st) {
-  if (DMB_OPT(4) == 1 || !ws) return -1;   // (development option 4 = 1: deconv3d_kernel)
-  if ((((uintptr_t)ws) & 3) != 0) return fail(DMB_EINVAL, "deconv3d: misaligned workspace");
-  if (!(Co == 32 || Co == 64) || Ci % 16 != 0 || Ci < 32 || W % 4 != 0 || Wout % 4 != 0) return -1;   // (>= 2 chunks in every class)
-  if ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)res) & 15) != 0) return -1;
-  if ((long long)16 * D * H * W * 4 >= 0x7fffffffLL || (long long)Co * 8 * D * H * W * 4 >= 0x7fffffffLL) return -1;
-  // 28-column tiles where they compute fewer columns than 60-column ones (80 input columns: 96 against 128); (round 6) tiles of 32 /
-  // 64 REAL columns (a longer staged row) where those compute fewer still: 64 input columns 64 against 96, 32 columns 32 against
-  // 64, 156 (KITTI) 160 against 192.  Same arithmetic per output whatever the tile.
-  const bool narrow = cdiv(W, 28) * 32 < cdiv(W, 60) * 64;
-  const int c_old = narrow ? cdiv(W, 28) * 32 : cdiv(W, 60) * 64, c_f32 = cdiv(W, 32) * 32, c_f64 = cdiv(W, 64) * 64;
-  // (a tie between 60- and 64-column tiles -- 120 input columns: 2 x 64 computed either way -- goes to the 64-column form, whose tiles
-  // start on 512-byte boundaries of the output rows: 849-865 -> 829 us for conv6 at [4, 64, 24, 68, 120] alone
-  // (scripts/attic/zy_b1_tile_probe.py), equal within the noise inside the step: 807 against 803 us under rocprofv3)
-  int full = c_f64 <= c_old && c_f64 <= c_f32 ? 2 : (c_f32 < c_old ? 1 : 0);
-  if (DMB_OPT(29) == 1) full = 0;                      // (development option 29: 1 = never, 2 / 3 = force the 32- / 64-column form)
-  if (DMB_OPT(29) >= 2) full = DMB_OPT(29) - 1;
-  // (round 6) A 64-channel launch of about one item per workgroup slot (conv5 of one 544x960 pair: 816 items of weight 1 .. 4 on
-  // 768 slots) is faster on deconv3d_kernel's items with both y parities: 0.099 -> 0.069 ms at [1, 64, 12, 34, 60]; equal at the
-  // KITTI shape and from two pairs on (scripts/kbench_hg.py, KB_B = 1 / 2).  Same arithmetic, bit-identical results.
-  if (Co == 64 && Wout == 2 * W && !DMB_OPT(28)) {   // (development option 28: keep the work-queue form)
-    const long long items = 4LL * B * cdiv(W, narrow ? 28 : 60) * H * cdiv(D, 2);
-    if (4 * items <= 5LL * 3 * num_cus()) return -1;
-  }
-  if (Co == 32) {
-    if (full == 2) return launch_zy<ZYCfg<32, 2, true>>(x, wp, scale, shift, res, y, B, Ci, D, H, W, Wout, relu, ws, st);
-    if (full == 1) return launch_zy<ZYCfg<32, 1, true>>(x, wp, scale, shift, res, y, B, Ci, D, H, W, Wout, relu, ws, st);
-    return narrow ? launch_zy<ZYCfg<32, 1>>(x, wp, scale, shift, res, y, B, Ci, D, H, W, Wout, relu, ws, st)
-                  : launch_zy<ZYCfg<32, 2>>(x, wp, scale, shift, res, y, B, Ci, D, H, W, Wout, relu, ws, st);
-  }
-  if (full == 2) return launch_zy<ZYCfg<64, 2, true>>(x, wp, scale, shift, res, y, B, Ci, D, H, W, Wout, relu, ws, st);
-  if (full == 1) return launch_zy<ZYCfg<64, 1, true>>(x, wp, scale, shift, res, y, B, Ci, D, H, W, Wout, relu, ws, st);
-  return narrow ? launch_zy<ZYCfg<64, 1>>(x, wp, scale, shift, res, y, B, Ci, D, H, W, Wout, relu, ws, st)
-                : launch_zy<ZYCfg<64, 2>>(x, wp, scale, shift, res, y, B, Ci, D, H, W, Wout, relu, ws, st);
+// The work-queue tile of plan config K (deconv3d_plan.h: ZY_TILE; 32 output channels first)
+int deconv3d_zy_launch(int cfg, const DeconvArgs& a, int* ws) {
+  auto run = [&](auto k) {
+    constexpr int K = decltype(k)::value, T = K % ZY_TILES;
+    if constexpr (T < ZY_BUILT) return launch_zy<ZYCfg<K < ZY_TILES ? 32 : 64, ZY_TILE[T].mt, ZY_TILE[T].full>>(a, ws);
+    return fail(DMB_EUNSUPPORTED, "deconv3d: the plain 60-column work-queue tile exists in the development build only");
+  };
+  return deconv_visit(cfg, run, std::make_integer_sequence<int, 2 * ZY_TILES>{});
 }
 
 }  // namespace dmb

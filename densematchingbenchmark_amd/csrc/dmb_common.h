@@ -111,18 +111,11 @@ __device__ __forceinline__ int cd_row(int r, int h) { return (r & 3) + 8 * (r >>
 
 #endif  // __HIPCC__
 
-// csrc/deconv3d_zy.hip: the (tile, z parity, y parity) form of the transposed convolution; -1 = does not apply.
-// `workspace`: DMB_DECONV3D_WORKSPACE_BYTES of device memory holding zeros (see include/dmb_hip.h); the launch leaves it zeroed.
-int deconv3d_zy_try(const float* x, const float* wp, const float* scale, const float* shift, const float* res, float* y,
-                    int B, int Ci, int Co, int D, int H, int W, int Wout, int relu, int* workspace, hipStream_t st);
-
 // csrc/conv3d_sk.hip: split-K form of the stride-1 / stride-2 convolution for launches that do not fill the chip; -1 = does not apply.
 int conv3d_sk_try(int variant, const float* x, const float* wp, const float* scale, const float* shift, const float* res, float* y,
                   int B, int Ci, int Co, int D, int H, int W, int stride, int relu, hipStream_t st);
 
 int conv2d_sk_try(const float* x, const float* wp, const float* scale, const float* shift, const float* res, float* y, int B, int Ci,
                   int Co, int H, int W, int dilation, int relu, int in_ctot, int out_ctot, int res_ctot, hipStream_t st);
-int deconv3d_sk_try(int variant, const float* x, const float* wp, const float* scale, const float* shift, const float* res, float* y,
-                    int B, int Ci, int Co, int D, int H, int W, int Wout, int relu, hipStream_t st);
 
 }  // namespace dmb

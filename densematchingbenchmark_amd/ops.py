@@ -524,19 +524,22 @@ def zero_columns_(t, x0):
     return t
 
 
+DECONV_PLAN_SPLIT_K, DECONV_PLAN_QUEUE, DECONV_PLAN_PARITY = 1, 2, 3   # dmb_deconv3d_k3s2_plan: the form, bits 8.. of a plan code
+
+
 def padded_rows_applicable(x, Co):
     """Whether a [B, Ci, D, H, W] tensor whose rows are NOT a 16-byte multiple (W % 4 != 0) can go through a stride-1 unit and a
     transposed unit with its rows padded to the next multiple of 4 (zero padding columns): the transposed kernel's padded-row
-    form needs an even W with 2 W % 4 == 0 ... i.e. W % 4 == 2, Co in (32, 64), whole 16-channel chunks."""
-    W, Ci = x.shape[-1], x.shape[1]
-    if not (x.is_cuda and W % 4 == 2 and Co in (32, 64) and Ci % 16 == 0 and Ci >= 32):
+    form needs an even W with 2 W % 4 == 0 ... i.e. W % 4 == 2, and the library's work-queue kernels for the padded launch."""
+    B, Ci, D, H, W = x.shape
+    if not (x.is_cuda and W % 4 == 2):
         return False
-    # ... and what csrc/deconv3d_zy.hip::deconv3d_zy_try checks besides (it is the only form that takes a row-padded input: if it
-    # declined, dmb_deconv3d_k3s2_f32 would fail with DMB_EUNSUPPORTED where the unpadded path has a fallback): 16 input channels of
-    # one batch item and one batch item of the output below 2 GiB; 16-byte alignment holds for every tensor the allocator hands out
-    D, H = x.shape[2], x.shape[3]
-    Wp = (W + 3) // 4 * 4
-    return 16 * D * H * Wp * 4 < 2 ** 31 - 1 and Co * 8 * D * H * Wp * 4 < 2 ** 31 - 1 and x.data_ptr() % 16 == 0
+    # The work-queue form is the only one that takes a row-padded input at every launch size (a refused launch would fail with
+    # DMB_EUNSUPPORTED where the unpadded path has a fallback), so ask what the library plans for the padded launch under the
+    # single-chain flag, which rules the size-dependent split-K form out.  x enters with its own alignment, and 16-byte alignment
+    # holds for every other tensor the allocator hands out.
+    plan = _lib.load().dmb_deconv3d_k3s2_plan(B, Ci, Co, D, H, (W + 3) // 4 * 4, 2 * W, min(x.data_ptr() & -x.data_ptr() or 16, 16), 16, 16, 16, 1, 0)
+    return plan >> 8 == DECONV_PLAN_QUEUE
 
 
 CATCONV_CH = 128   # channel count of the per-dz map tensors: 3 * Co used (Co <= 32), the rest are zero-weight rows

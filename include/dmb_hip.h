@@ -44,7 +44,7 @@ extern "C" {
 
 #define DMB_MAX_DISP_SAMPLES 256 /* upper bound on the number of disparity samples D */
 
-/* ABI version: bumped whenever a signature below changes (8: dmb_bn_train_fwd_f32, dmb_catconv_pack_weights_f32, dmb_conv3d_pack_weights_multi_f32, dmb_cat_first_wgrad_maps_f32, dmb_conv3d_k3_bnstats_f32 and dmb_bn_train_act_f32 added, dmb_bn_act_bwd_f32 takes the gradient its
+/* ABI version: bumped whenever a signature below changes (9: dmb_deconv3d_k3s2_plan added; 8: dmb_bn_train_fwd_f32, dmb_catconv_pack_weights_f32, dmb_conv3d_pack_weights_multi_f32, dmb_cat_first_wgrad_maps_f32, dmb_conv3d_k3_bnstats_f32 and dmb_bn_train_act_f32 added, dmb_bn_act_bwd_f32 takes the gradient its
  * skip operand already holds (`dres_acc`); 7: DMB_CONV_SINGLE_CHAIN in the `relu` argument of the convolution
  * entry points, `flags` argument of dmb_conv3d_k3_c1_f32; 6: dmb_stereo_pad_normalize_f32 / _u8 added; 5: dmb_fast_fms_bwd_f32 takes a mode, the forward's norm and an
  * optional gradient buffer for per-pixel samples; 4: workspace argument of dmb_deconv3d_k3s2_f32, the merged-heads entry
@@ -270,6 +270,20 @@ int dmb_conv3d_k3_head_f32(const float* x, const float* wpack, const float* scal
 int dmb_deconv3d_k3s2_f32(const float* x, const float* wpack, const float* scale, const float* shift,
                           const float* residual, float* y, int B, int Ci, int Co, int D, int H, int W, int Wout,
                           int relu, void* workspace, void* stream);
+/* What dmb_deconv3d_k3s2_f32 would run for a launch, without launching anything or touching a device: a pure function of its
+ * arguments.  Pointers enter as their alignment in bytes (a power of two; 16 or more = 16-byte aligned; 16 for a NULL residual;
+ * workspace_align 0 = no workspace); single_chain: whether DMB_CONV_SINGLE_CHAIN is set; ncu: the device's compute units, or
+ * <= 0 for the current device's (256 where there is none).  Returns
+ *   (form << 8) | tile   with form 1 = split-K over the waves of a workgroup: tile 0 (16 x 2 input positions, four waves);
+ *                        form 2 = work queue (needs the workspace; the only form besides split-K that takes Wout < 2 W):
+ *                          tile 0 = 28, 1 = 32, 2 = 64 real input columns per item (+ 4 for 64 output channels);
+ *                        form 3 = two-parity items, static walk: tile 0 = 60 columns with dword staging, 1 = 60 columns with 16-byte
+ *                          staging and the 8-byte epilogue, 2 = 60 columns with the 16-byte epilogue, 3 / 4 = 2 rows x 28 columns with
+ *                          the 8- / 16-byte epilogue (+ 5 for 64 output channels);
+ *   or -DMB_EINVAL / -DMB_EUNSUPPORTED where the launch would be refused with that code (dmb_last_error() then names the reason).
+ * Every form computes the same fma chain per output except split-K, which dmb_deconv3d_k3s2_f32 picks for small launches only. */
+int dmb_deconv3d_k3s2_plan(int B, int Ci, int Co, int D, int H, int W, int Wout, int x_align, int y_align, int residual_align,
+                           int workspace_align, int single_chain, int ncu);
 
 /* Conv3d, kernel 3, padding 1, stride 1 along D and stride_hw along H and W (DeepPruner's HWHourglass,
  * cost_processors/utils/hw_hourglass.py:31-74).  x: [B, Ci, D, H, W]; y: [B, Co, D, (H - 1) / stride_hw + 1,

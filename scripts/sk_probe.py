@@ -1,6 +1,6 @@
 """Development aid (round 6): the split-K convolution (csrc/conv3d_sk.hip) and the split-channel head (conv3d_c1s_kernel) --
 correctness of every variant against torch CPU on awkward shapes, then time per variant against the full-grid kernels at the
-hourglass shapes of one pair (BASELINE configs[0], 544x960, KITTI).  Development library (options 23 / 24).  KB_B = batch."""
+hourglass shapes of one pair (BASELINE configs[0], 544x960, KITTI).  Development library (options 23 / 24 / 25).  KB_B = batch."""
 import os
 os.environ.setdefault("DMB_LIB", "dev")
 import sys
@@ -94,8 +94,8 @@ def check():
                 ref = ref + res
             if relu is True:
                 ref = F.relu(ref)
-            for v in (0, 1, 2, 3, 4):
-                lib.dmb_dev_set_option(25, 1 if v == 0 else v + 1)
+            for v in (0, 1):   # (development option 25: 1 = never the split-K form, 2 = always)
+                lib.dmb_dev_set_option(25, v + 1)
                 got = ops.deconv3d_k3s2(x.to(dev), wp, Co, sc.to(dev), sh.to(dev), res.to(dev) if use_res else None, relu)
                 err = (got.cpu() - ref).abs().max().item()
                 if not err <= 3e-5:
@@ -177,8 +177,8 @@ for D, H, W in SHAPES:
         od = torch.empty_like(rd)
         fd = lambda: ops.deconv3d_k3s2(xd, wpd, Co, s1, s0, rd, True, out=od)   # noqa: E731
         fl = 2.0 * 27 * Ci * Co * xd[:, 0].numel()
-        for v, what in ((0, "full-grid kernel"), (1, "split-K 16x2, 8 waves"), (2, "split-K 32x2, 8 waves"), (3, "split-K 16x2, 4 waves"), (4, "split-K 32x2, 4 waves")):
-            lib.dmb_dev_set_option(25, 1 if v == 0 else v + 1)
+        for v, what in ((0, "full-grid kernel"), (1, "split-K 16x2, 4 waves")):
+            lib.dmb_dev_set_option(25, v + 1)
             line(name + ": " + what, timeit(fd), fl, timeit_graph(fd))
         lib.dmb_dev_set_option(25, 0)
     x = torch.randn(B, 32, D, H, W, device=dev)

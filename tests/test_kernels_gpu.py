@@ -1053,6 +1053,67 @@ def test_deconv3d_parity_class_items_match_the_two_parity_form(dev, Ci, Co, shap
     assert torch.equal(again, auto) and torch.equal(again, ops.deconv3d_k3s2(x, wp, Co, sc.to(dev), sh.to(dev), res, True, workspace=None))
 
 
+def _at_alignment(t, dev, al):
+    """The same values on the device at an address that is ``al`` (4, 8 or 16) bytes aligned and no more."""
+    if al >= 16:
+        return t.to(dev).contiguous()
+    buf = torch.empty(t.numel() + 4, dtype=torch.float32, device=dev)
+    v = buf[al // 4:al // 4 + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.data_ptr() % 16 == al and v.is_contiguous()
+    return v
+
+
+def test_deconv3d_every_planned_form(dev):
+    """Every kernel form and tile dmb_deconv3d_k3s2_f32 can run (csrc/deconv3d_plan.h), each at the first -- smallest -- launch of
+    tests/test_deconv3d_plan_host.py's recorded table that the plan gives that form: the query names the form for the very tensors
+    of the launch, the result is within 2e-5 of the CPU transposed convolution (with the affine, alone and with skip operand +
+    ReLU), and bit-identical to the two-parity form without a workspace on aligned operands -- the same fma chain per output --
+    except for the split-K form, which is reproducible instead.  A row-padded launch is compared with the unpadded one."""
+    from densematchingbenchmark_amd import _lib
+    from tests.test_deconv3d_plan_host import CASES, REACHABLE
+    ops, lib = _ops(), _lib.load()
+    first = {}
+    for c in CASES:
+        first.setdefault(c[13], c)
+    assert REACHABLE <= set(first)
+    before = ops.split_k()
+    try:
+        for code in sorted(REACHABLE):
+            label, B, Ci, Co, D, H, W, Wout, xa, ya, ra, wsa, sc = first[code][:13]
+            assert B * D * H <= 8 and W <= 80, label
+            Wi = Wout // 2                                   # real input columns; the rest of a padded row holds zeros
+            xc = _rand((B, Ci, D, H, W), 801)
+            xc[..., Wi:] = 0.0
+            wc = _rand((Ci, Co, 3, 3, 3), 802, 1.0 / math.sqrt(Ci * 27 / 8))
+            sc_, sh_ = _affine(Co, 803)
+            ref = F.conv_transpose3d(xc[..., :Wi], wc, None, stride=2, padding=1, output_padding=1) * sc_.view(1, -1, 1, 1, 1) + sh_.view(1, -1, 1, 1, 1)
+            resc = _rand(ref.shape, 804)
+            x, res = _at_alignment(xc, dev, xa), _at_alignment(resc, dev, ra)
+            wp = ops.pack_deconv3d_weights(wc.to(dev))
+            ws = torch.zeros(_lib_ws_ints(), dtype=torch.int32, device=dev) if wsa else None
+            ops.set_split_k(not sc)
+            for r, rc, relu in ((None, None, False), (res, resc, True)):
+                out = _at_alignment(torch.zeros(ref.shape), dev, ya)
+                al = lambda t: min(t.data_ptr() & -t.data_ptr(), 16)   # noqa: E731
+                plan = lib.dmb_deconv3d_k3s2_plan(B, Ci, Co, D, H, W, Wout, al(x), al(out), 16 if r is None else al(r), 16 if wsa else 0, sc, 0)
+                # (a launch without the skip operand has every operand but x and y aligned: its plan may be the aligned tile's)
+                assert plan == code or (r is None and ra < 16), (label, hex(plan))
+                got = ops.deconv3d_k3s2(x, wp, Co, sc_.to(dev), sh_.to(dev), r, relu, workspace=ws, out=out, out_width=Wout if Wout < 2 * W else None)
+                want = ref if r is None else F.relu(ref + rc)
+                assert got.shape == want.shape and (got.cpu() - want).abs().max().item() <= 2e-5, label
+                assert ws is None or int(ws.abs().sum().item()) == 0
+                if code >> 8 == ops.DECONV_PLAN_SPLIT_K:
+                    again = ops.deconv3d_k3s2(x, wp, Co, sc_.to(dev), sh_.to(dev), r, relu, workspace=ws, out_width=Wout if Wout < 2 * W else None)
+                else:
+                    ops.set_split_k(False)
+                    again = ops.deconv3d_k3s2(xc[..., :Wi].contiguous().to(dev), wp, Co, sc_.to(dev), sh_.to(dev), None if r is None else rc.to(dev), relu, workspace=None)
+                    ops.set_split_k(not sc)
+                assert torch.equal(got, again), (label, relu)
+    finally:
+        ops.set_split_k(before)
+
+
 # ------------------------------------------------------------------------------------- spatial propagation scan (dmb.ops.spn)
 @pytest.mark.parametrize("horizontal,reverse", [(True, False), (True, True), (False, False), (False, True)])
 @pytest.mark.parametrize("shape", [(2, 3, 6, 9), (1, 2, 64, 80), (1, 1, 1100, 5), (1, 2, 7, 1500)])
