@@ -26,7 +26,7 @@ _P = _c_void_p  # device pointer
 _HI = ctypes.POINTER(ctypes.c_int)  # host int array
 _HF = ctypes.POINTER(ctypes.c_float)  # host float array
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 # name -> (restype, argtypes)
 SIGNATURES = {
@@ -60,6 +60,7 @@ SIGNATURES = {
     "dmb_conv3d_k3_head_f32": (_c_int, [_P] * 5 + [_c_float, _P, _P, _P] + [_c_int] * 6 + [_P]),
     "dmb_deconv3d_k3s2_f32": (_c_int, [_P, _P, _P, _P, _P, _P] + [_c_int] * 8 + [_P, _P]),
     "dmb_deconv3d_k3s2_plan": (_c_int, [_c_int] * 13),
+    "dmb_conv3d_k3_plan": (_c_int, [_c_int] * 12),
     "dmb_conv3d_k3_hw_f32": (_c_int, [_P, _P, _P, _P, _P, _P] + [_c_int] * 8 + [_P]),
     "dmb_deconv3d_k3_hw_f32": (_c_int, [_P, _P, _P, _P, _P, _P] + [_c_int] * 7 + [_P]),
     "dmb_zero_columns_f32": (_c_int, [_P, _c_ll, _c_int, _c_int, _P]),

@@ -108,10 +108,10 @@ extern "C" int dmb_conv3d_pack_weights_multi_f32(const void* jobs_device, int nj
 // A full-grid kernel gives one wave the whole chain of 27 Ci / 2 MFMAs of a tile, in chunks of two channels behind a barrier each:
 // with fewer tile chains than SIMDs a launch costs ~1 us per chunk whatever its arithmetic (31-35 us for 64 channels).  Split-K
 // puts eight waves on a tile.  Units: 32-voxel column tiles (16 x 2 row pairs) x 32-channel row tiles.
-static int sk_variant(int B, int Ci, int Co, int D, int H, int W, int stride) {
+static int sk_variant(int B, int Ci, int Co, int D, int H, int W, int stride, int ncu) {
   const int Do = (D - 1) / stride + 1, Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
   const long long tiles = (long long)B * Do * cdiv(Ho, 2) * cdiv(Wo, 16);
-  const int ntt = Co / 32, ncu = num_cus();
+  const int ntt = Co / 32;
   // measured (profiles/r06_sk_probe.log, one MI355X): [1, 64, 4, 16, 32] 64 -> 64: stride 1 32.4 -> 12.8 us, stride 2 (from
   // [1, 64, 8, 32, 64]) 33.8 -> 14.9 us with one row tile per workgroup (128 workgroups); [1, 32, 16, 64, 128] -> 64 channels at
   // stride 2: 31.6 -> 22.0 us with 32 x 2 voxels x both row tiles (256 workgroups; 32 input channels = 2 pairs per wave keep the
@@ -122,30 +122,48 @@ static int sk_variant(int B, int Ci, int Co, int D, int H, int W, int stride) {
   return 0;
 }
 
-extern "C" int dmb_conv3d_k3_f32(const float* x, const float* wpack, const float* scale, const float* shift,
-                                 const float* residual, float* y, int B, int Ci, int Co, int D, int H, int W,
-                                 int stride, int relu, void* stream) {
-  if (!x || !wpack || !y || B <= 0 || Ci <= 0 || D <= 0 || H <= 0 || W <= 0) return fail(DMB_EINVAL, "conv3d: bad argument");
+// The plan of a launch: every condition that decides among the family's forms, and every refusal (conv3d_mfma.h has the codes)
+static int conv3d_plan(const ConvDesc& d, const char** why) {
+  const int B = d.B, Ci = d.Ci, Co = d.Co, D = d.D, H = d.H, W = d.W, stride = d.stride;
+  auto refuse = [&](int err, const char* msg) { return *why = msg, -err; };
+  if (B <= 0 || Ci <= 0 || D <= 0 || H <= 0 || W <= 0) return refuse(DMB_EINVAL, "conv3d: bad argument");
   if ((long long)8 * D * H * W * 4 >= 0x7fffffffLL)
-    return fail(DMB_EUNSUPPORTED, "conv3d: 8 channels of one batch item must stay below 2 GiB (32-bit buffer offsets)");
-  const bool out_small = (long long)Co * D * H * W * 4 < 0x7fffffffLL;   // the vector epilogue addresses the whole output item
-  hipStream_t st = (hipStream_t)stream;
-  const bool single_chain = (relu & DMB_CONV_SINGLE_CHAIN) != 0;
-  relu &= 0xff;
-  relu |= (DMB_OPT(6) & 0xff) << 8;                    // (development build: diagnostics, see the kernels)
-  const int relu_s1 = relu | (DMB_OPT(14) << 16);      // (development build: start-up stagger unit of the stride-1 kernels)
+    return refuse(DMB_EUNSUPPORTED, "conv3d: 8 channels of one batch item must stay below 2 GiB (32-bit buffer offsets)");
   if ((stride == 1 || stride == 2) && (Co == 32 || Co == 64)) {
     // (round 6) launches that leave most of the chip idle: the K chain of a tile split over the eight waves of a workgroup
     // (csrc/conv3d_sk.hip).  DMB_OPT(23) (development build): 1 = never, k >= 2 = force variant k - 1.
-    int v = single_chain ? 0 : sk_variant(B, Ci, Co, D, H, W, stride);
+    int v = d.single_chain ? 0 : sk_variant(B, Ci, Co, D, H, W, stride, d.ncu);
     if (DMB_OPT(23) == 1) v = 0;
     if (DMB_OPT(23) >= 2) v = DMB_OPT(23) - 1;
-    if (v > 0) {
-      const int rc = conv3d_sk_try(v, x, wpack, scale, shift, residual, y, B, Ci, Co, D, H, W, stride, relu & 0xff, st);
-      if (rc != -1) return rc;
-    }
+    if (v > 0 && conv3d_sk_applies(v, d)) return (CONV_SPLIT_K << 8) | (v + 4 * (stride - 1));
   }
-  if (stride == 1) return conv3d_s1_run(x, wpack, scale, shift, residual, y, B, Ci, Co, D, H, W, relu_s1, out_small, st);
-  if (stride == 2) return conv3d_s2_run(x, wpack, scale, shift, residual, y, B, Ci, Co, D, H, W, relu, st);
-  return conv3d_unsupported();
+  if (stride == 1) return conv3d_s1_plan(d, why);
+  if (stride == 2) return conv3d_s2_plan(d, why);
+  return refuse(DMB_EUNSUPPORTED, CONV3D_UNSUPPORTED);
+}
+
+extern "C" int dmb_conv3d_k3_plan(int B, int Ci, int Co, int D, int H, int W, int stride, int x_align, int y_align, int residual_align,
+                                  int single_chain, int ncu) {
+  const char* why = "";
+  const int plan = conv3d_plan({B, Ci, Co, D, H, W, stride, x_align, y_align, residual_align, single_chain != 0, ncu > 0 ? ncu : num_cus()}, &why);
+  set_last_error(why);
+  return plan;
+}
+
+extern "C" int dmb_conv3d_k3_f32(const float* x, const float* wpack, const float* scale, const float* shift,
+                                 const float* residual, float* y, int B, int Ci, int Co, int D, int H, int W,
+                                 int stride, int relu, void* stream) {
+  if (!x || !wpack || !y) return fail(DMB_EINVAL, "conv3d: bad argument");
+  const char* why = "";
+  const int plan = conv3d_plan({B, Ci, Co, D, H, W, stride, align_of(x), align_of(y), align_of(residual), (relu & DMB_CONV_SINGLE_CHAIN) != 0,
+                                num_cus()}, &why);
+  if (plan < 0) return fail(-plan, why);
+  hipStream_t st = (hipStream_t)stream;
+  relu &= 0xff;
+  if (plan >> 8 == CONV_SPLIT_K)
+    return conv3d_sk_launch((plan & 0xff) - 4 * (stride - 1), x, wpack, scale, shift, residual, y, B, Ci, Co, D, H, W, stride, relu, st);
+  relu |= (DMB_OPT(6) & 0xff) << 8;                    // (development build: diagnostics, see the kernels)
+  const int relu_s1 = relu | (DMB_OPT(14) << 16);      // (development build: start-up stagger unit of the stride-1 kernels)
+  if (plan >> 8 == CONV_S2) return conv3d_s2_run(plan, x, wpack, scale, shift, residual, y, B, Ci, D, H, W, relu, st);
+  return conv3d_s1_run(plan, x, wpack, scale, shift, residual, y, B, Ci, D, H, W, relu_s1, st);
 }

@@ -1,7 +1,7 @@
 // Stride-1 and stride-2 3x3x3 convolutions of the cost aggregators: the FP32-MFMA implicit GEMM described at the head of conv3d.hip
 // (roles, data flow per workgroup).  First the stride-1 kernel, its tile shapes and the estimate that chooses among them, the
 // BatchNorm-statistics form of the training path and the fused 32 -> 1 classifier head; then the stride-2 kernel and the estimate of
-// its tile height.  dmb_conv3d_k3_f32 (conv3d.hip) reaches them through conv3d_s1_run / conv3d_s2_run.
+// its tile height.  dmb_conv3d_k3_f32 (conv3d.hip) reaches them through conv3d_s1_plan / conv3d_s2_plan and conv3d_s1_run / conv3d_s2_run.
 //
 // Why the two share a translation unit: the compiler propagates constants and value ranges into the small helpers of dmb_common.h /
 // conv3d_mfma.h (cdiv, store_tile<1>, ...) from ALL their callers in the unit before it inlines them.  Alone, the stride-2 kernels
@@ -620,7 +620,7 @@ static auto s1_visit(int pick, F&& f, std::index_sequence<I...>) {
   (void)(((pick == (int)I || I + 1 == sizeof...(I)) && ((r = f(std::tuple_element_t<I, Tiles>{})), true)) || ...);
   return r;
 }
-static double s1_cost(const S1Tile& t, int B, int D, int H, int W) {
+static double s1_cost(const S1Tile& t, int B, int D, int H, int W, int ncu) {
   const long long n = t.lin ? (long long)B * cdiv(D, t.tz) * cdiv(H * W, 64)
                             : (long long)B * cdiv(D, t.tz) * cdiv(H, t.ty) * cdiv(W, t.tx);
   // What a CU holds is ceil(n / CUs) workgroups, each with one wave per SIMD running `mt` column tiles -- serial chains of
@@ -629,16 +629,16 @@ static double s1_cost(const S1Tile& t, int B, int D, int H, int W) {
   // n = wpe x CUs that misjudged launches around one round -- batch 1, small images.)  Checked against every candidate measured
   // so far: profiles/r04_kbench_hg*.log (batch 4: 240 / 120 / 60 and 312 / 156 columns) and profiles/r05_kbench_small.log (batch 1
   // at 256x512 / D 64, 544x960 and 384x1248) -- the estimate ranks them as measured.
-  return (double)cdiv_ll(n, num_cus()) * (t.mt + 0.1) / t.eff;
+  return (double)cdiv_ll(n, ncu) * (t.mt + 0.1) / t.eff;
 }
 // index of the cheapest candidate (ties: the earlier one); DMB_OPT(19) = k > 0 forces candidate k - 1 (development build)
-static int s1_pick(const S1Tile* cand, const bool* ok, int n, int B, int D, int H, int W) {
+static int s1_pick(const S1Tile* cand, const bool* ok, int n, int B, int D, int H, int W, int ncu) {
   if (DMB_OPT(19) > 0 && DMB_OPT(19) <= n && ok[DMB_OPT(19) - 1]) return DMB_OPT(19) - 1;
   int best = -1;
   double bc = 0.0;
   for (int i = 0; i < n; ++i) {
     if (!ok[i]) continue;
-    const double c = s1_cost(cand[i], B, D, H, W);
+    const double c = s1_cost(cand[i], B, D, H, W, ncu);
     if (best < 0 || c < bc) best = i, bc = c;
   }
   return best;
@@ -663,13 +663,13 @@ constexpr int S1_HEAD_PICK = 0;
 static_assert(std::is_base_of_v<std::tuple_element_t<S1_HEAD_PICK, S1Tiles32>, S1HeadCfg>, "the head's tile is a candidate of the plain launch");
 template <class F>
 static auto s1_visit32(int pick, F&& f) { return s1_visit<S1Tiles32>(pick, f, std::make_index_sequence<4>{}); }
-static int s1_pick32(int B, int D, int H, int W) {
+static int s1_pick32(int B, int D, int H, int W, int ncu) {
   static constexpr auto cand = s1_tiles<S1Tiles32>(S1Eff32, std::make_index_sequence<4>{});
   const bool ok[4] = {true, true, true, true};
-  int pick = s1_pick(cand.data(), ok, 4, B, D, H, W);
+  int pick = s1_pick(cand.data(), ok, 4, B, D, H, W, ncu);
   // (round 6) a launch of at most ONE 32 x 4 workgroup per CU: two 32 x 2 workgroups per CU instead, so that one's prologue and
   // epilogue fall under the other's multiply phase ([1, 32, 16, 64, 128]: 57.6 -> 55.7 us, profiles/r06_sk_probe_midsizes.log)
-  if (pick == 2 && DMB_OPT(19) == 0 && (long long)B * cdiv(D, 4) * cdiv(H, 4) * cdiv(W, 32) <= num_cus()) pick = 3;
+  if (pick == 2 && DMB_OPT(19) == 0 && (long long)B * cdiv(D, 4) * cdiv(H, 4) * cdiv(W, 32) <= ncu) pick = 3;
   return pick;
 }
 static long long s1_blocks32(int pick, int B, int D, int H, int W) {
@@ -690,38 +690,74 @@ using S1Tiles64 = std::tuple<S1Cfg<0, 64, 3, 64, 2, 2, 1, 16, 0, true>, S1Cfg<0,
                              S1Cfg<0, 64, 4, 32, 2, 2, 1, 8, 40>, S1Cfg<0, 64, 2, 16, 4, 2, 1, 16, 0>>;
 constexpr double S1Eff64[5] = {1.0, 1.0, 1.0, 1.0, 0.95};
 
-int conv3d_s1_run(const float* x, const float* wpack, const float* scale, const float* shift, const float* residual, float* y, int B,
-                  int Ci, int Co, int D, int H, int W, int relu_s1, bool out_small, hipStream_t st) {
-  auto run = [&](auto c) { return launch_s1<decltype(c)>(x, wpack, scale, shift, residual, y, B, Ci, D, H, W, relu_s1, st); };
-  // the vector path: 16-byte rows for staging, skip operand and stores
-  const bool vec = W % 4 == 0 && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)residual) & 15) == 0 && out_small && DMB_OPT(2) == 0;
-  const int tx = flat_tx(W);
-  if (Co == 32) {
+// f(C{}) for the instantiation a stride-1 plan code names: the one place where a code becomes a type, for the plan's own
+// workgroup count and for the launch
+template <class F>
+static auto s1_form(int plan, F&& f) {
+  const int form = plan >> 8, k = plan & 0xff;
 #ifdef DMB_DEV
-    if (DMB_OPT(0) == 1) return run(S1Cfg<0, 32, 4, 60, 2, 1, 0, 0>{});
-    // (round 6 experiment) chunks of 4 input channels for the 32-column tiles
-    if (vec && DMB_OPT(19) == 8) return run(S1Cfg<0, 32, 4, 32, 4, 1, 1, 16, 0>{});
-    if (vec && DMB_OPT(19) == 9) return run(S1Cfg<0, 32, 2, 32, 4, 1, 1, 16, 0>{});
+  if (form == CONV_S1_FLAT && k == CONV_DEV) return f(S1Cfg<0, 32, 4, 60, 2, 1, 0, 0>{});
+  // (round 6 experiment) chunks of 4 input channels for the 32-column tiles
+  if (form == CONV_S1_VEC && k == CONV_DEV) return f(S1Cfg<0, 32, 4, 32, 4, 1, 1, 16, 0>{});
+  if (form == CONV_S1_VEC && k == CONV_DEV + 1) return f(S1Cfg<0, 32, 2, 32, 4, 1, 1, 16, 0>{});
+  // (round 6 experiment) the 16 x 2 tile with chunks of 2 / 8 input channels (the library's: 4)
+  if (form == CONV_S1_VEC && k == CONV_DEV + 2) return f(S1Cfg<0, 64, 2, 16, 2, 2, 1, 16, 0>{});   // (the round-5 form of the tile: chunks of 2)
+  if (form == CONV_S1_VEC && k == CONV_DEV + 3) return f(S1Cfg<0, 64, 2, 16, 8, 2, 1, 16, 0>{});
 #endif
-    if (vec) return s1_visit32(s1_pick32(B, D, H, W), run);
-    return tx == 52 ? run(S1Cfg<0, 32, 4, 52, 2, 1, 1, 0, 0>{}) : run(S1Cfg<0, 32, 4, 60, 2, 1, 1, 0, 0>{});
+  if (form == CONV_S1_VEC) return k < 4 ? s1_visit32(k, f) : s1_visit<S1Tiles64>(k - 4, f, std::make_index_sequence<5>{});
+  if (form == CONV_S1_FLAT) {
+    if (k == 0) return f(S1Cfg<0, 32, 4, 60, 2, 1, 1, 0, 0>{});
+    if (k == 1) return f(S1Cfg<0, 32, 4, 52, 2, 1, 1, 0, 0>{});
+    if (k == 2) return f(S1Cfg<0, 64, 4, 60, 2, 2, 1, 0, 0>{});
+    return f(S1Cfg<0, 64, 4, 52, 2, 2, 1, 0, 0>{});
   }
-  if (Co == 64) {
+  // CONV_S1_C128, GC-Net's deepest level: 2 waves x 2 row tiles, 2-row tiles keep the accumulators at 160 registers
+  return f(S1Cfg<0, 128, 2, 60, 2, 2, 1, 0, 0>{});
+}
+
+int conv3d_s1_plan(const ConvDesc& d, const char** why) {
+  const int B = d.B, Co = d.Co, D = d.D, H = d.H, W = d.W;
+  const bool out_small = (long long)Co * D * H * W * 4 < 0x7fffffffLL;   // the vector epilogue addresses the whole output item
+  // the vector path: 16-byte rows for staging, skip operand and stores
+  const bool vec = W % 4 == 0 && d.x_align >= 16 && d.y_align >= 16 && d.res_align >= 16 && out_small && DMB_OPT(2) == 0;
+  const int flat = flat_tx(W) == 52 ? 1 : 0;
+  auto code = [](int form, int k) { return (form << 8) | k; };
+  int plan;
+  if (Co == 32) {
+    plan = vec ? code(CONV_S1_VEC, s1_pick32(B, D, H, W, d.ncu)) : code(CONV_S1_FLAT, flat);
+#ifdef DMB_DEV
+    if (vec && DMB_OPT(19) == 9) plan = code(CONV_S1_VEC, CONV_DEV + 1);
+    if (vec && DMB_OPT(19) == 8) plan = code(CONV_S1_VEC, CONV_DEV);
+    if (DMB_OPT(0) == 1) plan = code(CONV_S1_FLAT, CONV_DEV);
+#endif
+  } else if (Co == 64) {
     if (vec) {
       static constexpr auto cand = s1_tiles<S1Tiles64>(S1Eff64, std::make_index_sequence<5>{});
       const bool ok[5] = {W >= 32 && W <= 64 && (H * W) % 4 == 0 && DMB_OPT(13) == 0, true, true, true, true};
+      plan = code(CONV_S1_VEC, 4 + s1_pick(cand.data(), ok, 5, B, D, H, W, d.ncu));
 #ifdef DMB_DEV
-      // (round 6 experiment) the 16 x 2 tile with chunks of 2 / 8 input channels (the library's: 4)
-      if (DMB_OPT(19) == 6) return run(S1Cfg<0, 64, 2, 16, 2, 2, 1, 16, 0>{});   // (the round-5 form of the tile: chunks of 2)
-      if (DMB_OPT(19) == 7) return run(S1Cfg<0, 64, 2, 16, 8, 2, 1, 16, 0>{});
+      if (DMB_OPT(19) == 7) plan = code(CONV_S1_VEC, CONV_DEV + 3);
+      if (DMB_OPT(19) == 6) plan = code(CONV_S1_VEC, CONV_DEV + 2);
 #endif
-      return s1_visit<S1Tiles64>(s1_pick(cand.data(), ok, 5, B, D, H, W), run, std::make_index_sequence<5>{});
+    } else {
+      plan = code(CONV_S1_FLAT, 2 + flat);
     }
-    return tx == 52 ? run(S1Cfg<0, 64, 4, 52, 2, 2, 1, 0, 0>{}) : run(S1Cfg<0, 64, 4, 60, 2, 2, 1, 0, 0>{});
+  } else if (Co == 128) {
+    plan = code(CONV_S1_C128, 0);
+  } else {
+    return *why = CONV3D_UNSUPPORTED, -DMB_EUNSUPPORTED;
   }
-  if (Co == 128)   // GC-Net's deepest level: 2 waves x 2 row tiles, 2-row tiles keep the accumulators at 160 registers
-    return run(S1Cfg<0, 128, 2, 60, 2, 2, 1, 0, 0>{});
-  return conv3d_unsupported();
+  const long long nblk = s1_form(plan, [&](auto c) {
+    using C = decltype(c);
+    return (long long)B * (C::LIN ? cdiv(H * W, 64) : cdiv(W, C::TX) * cdiv(H, C::TY)) * cdiv(D, C::TZ);
+  });
+  if (nblk > 0x7fffffffLL) return *why = "conv3d: grid too large", -DMB_EUNSUPPORTED;
+  return plan;
+}
+
+int conv3d_s1_run(int plan, const float* x, const float* wpack, const float* scale, const float* shift, const float* residual, float* y,
+                  int B, int Ci, int D, int H, int W, int relu_s1, hipStream_t st) {
+  return s1_form(plan, [&](auto c) { return launch_s1<decltype(c)>(x, wpack, scale, shift, residual, y, B, Ci, D, H, W, relu_s1, st); });
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1014,17 +1050,35 @@ using S2Rows2 = S2Cfg<0, 64, 2, 30, 2, 2, true, 2, true>;
 using S2Rows1 = S2Cfg<0, 64, 1, 30, 2, 2, true, 1, true>;
 using S2Narrow = S2Cfg<0, 64, 4, 22, 2, 2, true>;
 
-int conv3d_s2_run(const float* x, const float* wpack, const float* scale, const float* shift, const float* residual, float* y, int B,
-                  int Ci, int Co, int D, int H, int W, int relu, hipStream_t st) {
-  auto run = [&](auto c) { return launch_s2<decltype(c)>(x, wpack, scale, shift, residual, y, B, Ci, D, H, W, relu, st); };
-  const bool v16 = W % 4 == 0 && ((uintptr_t)x & 15) == 0 && !DMB_OPT(3);   // 16-byte aligned input rows
+// f(C{}) for the instantiation a stride-2 plan index names (conv3d_mfma.h: S2_ROWS1 ...)
+template <class F>
+static auto s2_form(int k, F&& f) {
+#ifdef DMB_DEV
+  // (round 6 experiment) chunks of 4 input channels; A/B: four-wave workgroups
+  if (k == CONV_DEV) return f(S2Cfg<0, 64, 1, 30, 4, 2, true, 1, true>{});
+  if (k == CONV_DEV + 1) return f(S2Cfg<0, 64, 2, 30, 4, 2, true, 2, true>{});
+  if (k == CONV_DEV + 2) return f(S2Cfg<0, 64, 4, 30, 2, 2, true>{});
+#endif
+  if (k == S2_ROWS1) return f(S2Rows1{});
+  if (k == S2_ROWS2) return f(S2Rows2{});
+  if (k == S2_ROWS4) return f(S2Rows4{});
+  if (k == S2_NARROW) return f(S2Narrow{});
+  if (k == S2_ROWS4_DWORD) return f(S2Cfg<0, 64, 4, 30, 2, 2, true, 2>{});
+  if (k == S2_FLAT64) return f(S2Cfg<0, 64, 4, 30, 2, 2>{});
+  if (k == S2_FLAT32) return f(S2Cfg<0, 32, 4, 30, 2, 1>{});
+  return f(S2Cfg<0, 128, 4, 30, 2, 4>{});
+}
+
+static int s2_pick(const ConvDesc& d) {
+  const int B = d.B, Co = d.Co, D = d.D, H = d.H, W = d.W;
+  const bool v16 = W % 4 == 0 && d.x_align >= 16 && !DMB_OPT(3);   // 16-byte aligned input rows
   if (Co == 64 && v16) {
     // output positions computed per tile row: 32 with 30-column tiles, 24 with 22-column ones; the narrower tile wins at
     // the training-crop widths (Wo = 64: 3 x 96 against 3 x 128 positions per 4 rows, Wo = 32: 2 x 96 against 2 x 128)
     const int Wo = (W - 1) / 2 + 1, Ho = (H - 1) / 2 + 1, Do = (D - 1) / 2 + 1;
     // 8-byte epilogue: W % 4 == 0 makes Wo even; the output (and skip operand) base must be 8-byte aligned and one batch item
     // of the output addressable with 32-bit byte offsets
-    const bool pair_ok = ((((uintptr_t)y | (uintptr_t)residual) & 7) == 0) && (long long)Co * Do * Ho * Wo * 4 < 0x7fffffffLL;
+    const bool pair_ok = d.y_align >= 8 && d.res_align >= 8 && (long long)Co * Do * Ho * Wo * 4 < 0x7fffffffLL;
     const bool narrow = cdiv(Wo, 22) * 96 < cdiv(Wo, 30) * 128;
     // (round 5) Tile height by estimate.  What a CU holds is ceil(workgroups / CUs) workgroups, and one SIMD runs a workgroup's
     // column tiles one after the other -- 4 with the 4 x 30 eight-wave tiles, 3 with 4 x 22, 2 with two-row tiles, 1 with one-row
@@ -1033,7 +1087,7 @@ int conv3d_s2_run(const float* x, const float* wpack, const float* scale, const 
     // 64 -> 64 layer at batch 4, 201 -> 188 us on 1632 one-row ones), at the price of more halo rows per output: efficiencies
     // fitted to profiles/r05_s2_tile_probe.log and r05_kbench_small.log (same results bit for bit whatever the tile).
     const long long nz = (long long)B * cdiv(Do, 2);
-    const int ncu = num_cus();
+    const int ncu = d.ncu;
     const double c_old = (double)cdiv_ll(nz * (narrow ? cdiv(Wo, 22) : cdiv(Wo, 30)) * cdiv(Ho, 4), ncu) * (narrow ? 3.0 / 0.85 : 4.0);
     const double c_two = (double)cdiv_ll(nz * cdiv(Wo, 30) * cdiv(Ho, 2), ncu) * 2.0 / 0.97;
     const double c_one = (double)cdiv_ll(nz * cdiv(Wo, 30) * Ho, ncu) * 1.0 / 0.94;
@@ -1043,24 +1097,38 @@ int conv3d_s2_run(const float* x, const float* wpack, const float* scale, const 
     if (pair_ok && DMB_OPT(10) == 3) rows = 1;
     if (pair_ok && DMB_OPT(10) == 4) rows = 2;
     // (round 6 experiment) chunks of 4 input channels
-    if (pair_ok && DMB_OPT(10) == 5) return run(S2Cfg<0, 64, 1, 30, 4, 2, true, 1, true>{});
-    if (pair_ok && DMB_OPT(10) == 6) return run(S2Cfg<0, 64, 2, 30, 4, 2, true, 2, true>{});
+    if (pair_ok && DMB_OPT(10) == 5) return CONV_DEV;
+    if (pair_ok && DMB_OPT(10) == 6) return CONV_DEV + 1;
 #endif
-    if (rows == 1) return run(S2Rows1{});
-    if (rows == 2) return run(S2Rows2{});
-    if (narrow) return run(S2Narrow{});
+    if (rows == 1) return S2_ROWS1;
+    if (rows == 2) return S2_ROWS2;
+    if (narrow) return S2_NARROW;
 #ifdef DMB_DEV
     if (DMB_OPT(10) == 1)   // A/B: four-wave workgroups
-      return run(S2Cfg<0, 64, 4, 30, 2, 2, true>{});
+      return CONV_DEV + 2;
 #endif
     if (pair_ok && DMB_OPT(10) != 2)   // (A/B: 10 = 2 keeps the dword epilogue)
-      return run(S2Rows4{});
-    return run(S2Cfg<0, 64, 4, 30, 2, 2, true, 2>{});
+      return S2_ROWS4;
+    return S2_ROWS4_DWORD;
   }
-  if (Co == 64) return run(S2Cfg<0, 64, 4, 30, 2, 2>{});
-  if (Co == 32) return run(S2Cfg<0, 32, 4, 30, 2, 1>{});
-  if (Co == 128) return run(S2Cfg<0, 128, 4, 30, 2, 4>{});
-  return conv3d_unsupported();
+  return Co == 64 ? S2_FLAT64 : (Co == 32 ? S2_FLAT32 : (Co == 128 ? S2_FLAT128 : -1));
+}
+
+int conv3d_s2_plan(const ConvDesc& d, const char** why) {
+  const int k = s2_pick(d);
+  if (k < 0) return *why = CONV3D_UNSUPPORTED, -DMB_EUNSUPPORTED;
+  const int Do = (d.D - 1) / 2 + 1, Ho = (d.H - 1) / 2 + 1, Wo = (d.W - 1) / 2 + 1;
+  const long long nblk = s2_form(k, [&](auto c) {
+    using C = decltype(c);
+    return (long long)d.B * cdiv(Wo, C::TX) * cdiv(Ho, C::TY) * cdiv(Do, C::TZ);
+  });
+  if (nblk > 0x7fffffffLL) return *why = "conv3d: grid too large", -DMB_EUNSUPPORTED;
+  return (CONV_S2 << 8) | k;
+}
+
+int conv3d_s2_run(int plan, const float* x, const float* wpack, const float* scale, const float* shift, const float* residual, float* y,
+                  int B, int Ci, int D, int H, int W, int relu, hipStream_t st) {
+  return s2_form(plan & 0xff, [&](auto c) { return launch_s2<decltype(c)>(x, wpack, scale, shift, residual, y, B, Ci, D, H, W, relu, st); });
 }
 
 }  // namespace dmb
@@ -1076,14 +1144,14 @@ static bool s1_stats_applicable(const float* x, const float* y, int B, int Ci, i
 }
 extern "C" long long dmb_conv3d_k3_bnstats_partials(int B, int Ci, int Co, int D, int H, int W) {
   if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || !s1_stats_shape(Ci, Co, D, H, W)) return 0;
-  return s1_blocks32(s1_pick32(B, D, H, W), B, D, H, W);
+  return s1_blocks32(s1_pick32(B, D, H, W, num_cus()), B, D, H, W);
 }
 extern "C" int dmb_conv3d_k3_bnstats_f32(const float* x, const float* wpack, float* y, double* stats, int B, int Ci, int Co, int D, int H,
                                          int W, void* stream) {
   if (!x || !wpack || !y || !stats || B <= 0 || Ci <= 0 || D <= 0 || H <= 0 || W <= 0) return fail(DMB_EINVAL, "conv3d_bnstats: bad argument");
   if (!s1_stats_applicable(x, y, B, Ci, Co, D, H, W)) return fail(DMB_EUNSUPPORTED, "conv3d_bnstats: 32 output channels, 16-byte rows");
   hipStream_t st = (hipStream_t)stream;
-  return s1_visit32(s1_pick32(B, D, H, W), [&](auto c) { return launch_s1_stats<decltype(c)>(x, wpack, y, stats, B, Ci, D, H, W, st); });
+  return s1_visit32(s1_pick32(B, D, H, W, num_cus()), [&](auto c) { return launch_s1_stats<decltype(c)>(x, wpack, y, stats, B, Ci, D, H, W, st); });
 }
 
 // ---- 32 -> 32 classifier convolution + its 32 -> 1 head in one launch (+ the finishing pass) -----------------------------------
@@ -1098,7 +1166,7 @@ extern "C" long long dmb_conv3d_k3_head_workspace_floats(int B, int D, int H, in
   return s1_blocks32(S1_HEAD_PICK, B, D, H, W) * S1HeadCfg::OUT_FLOATS;
 }
 extern "C" int dmb_conv3d_k3_head_preferred(int B, int D, int H, int W) {
-  return s1_head_runs(B, D, H, W) && s1_pick32(B, D, H, W) == S1_HEAD_PICK;
+  return s1_head_runs(B, D, H, W) && s1_pick32(B, D, H, W, num_cus()) == S1_HEAD_PICK;
 }
 extern "C" int dmb_conv3d_head_pack_weights_f32(const float* w, float* wpack, void* stream) {
   if (!w || !wpack) return fail(DMB_EINVAL, "conv3d_head_pack_weights: bad argument");

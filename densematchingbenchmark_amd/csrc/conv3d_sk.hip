@@ -21,8 +21,8 @@
 // in the last bits (and with them batch 1 from batch 4 where this form is picked) -- both are FP32 evaluations of the same
 // convolution; the tests bound them against the FP64 yardstick instead of against each other.
 //
-// Which launches take this form is a cost estimate in dmb_conv3d_k3_f32 (conv3d.hip) and deconv_plan (deconv3d_plan.h); conv3d_sk_try returns -1 where the shape
-// does not qualify.
+// Which launches take this form is a cost estimate in conv3d_plan (conv3d.hip) and deconv_plan (deconv3d_plan.h); conv3d_sk_applies
+// tells the former where the shape does not qualify.
 #include "deconv3d_plan.h"
 
 namespace dmb {
@@ -288,37 +288,48 @@ static constexpr long long sk_lds_bytes(int Ci) {
 }
 
 // variant: 1 = 16 x 2 voxel tile, one 32-channel row tile per workgroup; 2 = 32 x 2 voxels, one row tile; 3 = 32 x 2 voxels, both row
-// tiles of a 64-channel layer (32 input channels only: the A fragments of a wave must fit its registers).  -1: the shape does not qualify.
-int conv3d_sk_try(int variant, const float* x, const float* wp, const float* scale, const float* shift, const float* res, float* y,
-                  int B, int Ci, int Co, int D, int H, int W, int stride, int relu, hipStream_t st) {
-  constexpr int NW = 8;
-  if (Ci % (2 * NW) != 0 || (Co != 32 && Co != 64) || W % 4 != 0 || (((uintptr_t)x) & 15) != 0) return -1;
-  const int Wo = (W - 1) / stride + 1;
-  if (Wo % 4 == 0 && ((((uintptr_t)y) | ((uintptr_t)res)) & 15) != 0) return -1;
-  if ((long long)(Ci / NW) * D * H * W * 4 >= 0x7fffffffLL) return -1;   // 32-bit offsets inside a wave's channels
-  const int NP = Ci / (2 * NW);
-#define DMB_SK(S, NT, XS, YS, NPR)                                                                             \
-  do {                                                                                                         \
-    using C = SKCfg<S, NW, NT, XS, YS, NPR>;                                                                   \
-    if (NP > NPR || sk_lds_bytes<C>(Ci) > 160 * 1024) return -1;                                               \
-    return launch_sk<C>(x, wp, scale, shift, res, y, B, Ci, Co, D, H, W, relu, st);                            \
-  } while (0)
+// tiles of a 64-channel layer (32 input channels only: the A fragments of a wave must fit its registers).
+// f(SKCfg{}) for the instantiation of (variant, stride, Co); -1 where this build holds none: the one place where a variant becomes a type.
+constexpr int SK_NW = 8;
+template <class F>
+static int sk_visit(int variant, int stride, int Co, F&& f) {
   // (variant 2 and the stride-1 form of variant 3 are never picked by sk_variant: measured, kept in the development build only)
   if (stride == 1) {
-    if (variant == 1) DMB_SK(1, 1, 1, 1, 4);
+    if (variant == 1) return f(SKCfg<1, SK_NW, 1, 1, 1, 4>{});
 #ifdef DMB_DEV
-    if (variant == 2) DMB_SK(1, 1, 2, 1, 4);
-    if (variant == 3 && Co == 64) DMB_SK(1, 2, 2, 1, 2);
+    if (variant == 2) return f(SKCfg<1, SK_NW, 1, 2, 1, 4>{});
+    if (variant == 3 && Co == 64) return f(SKCfg<1, SK_NW, 2, 2, 1, 2>{});
 #endif
   } else if (stride == 2) {
-    if (variant == 1) DMB_SK(2, 1, 1, 1, 4);
+    if (variant == 1) return f(SKCfg<2, SK_NW, 1, 1, 1, 4>{});
 #ifdef DMB_DEV
-    if (variant == 2) DMB_SK(2, 1, 2, 1, 4);
+    if (variant == 2) return f(SKCfg<2, SK_NW, 1, 2, 1, 4>{});
 #endif
-    if (variant == 3 && Co == 64) DMB_SK(2, 2, 2, 1, 2);
+    if (variant == 3 && Co == 64) return f(SKCfg<2, SK_NW, 2, 2, 1, 2>{});
   }
-#undef DMB_SK
   return -1;
+}
+
+// Everything the form requires of a launch (conv3d_plan, conv3d.hip, asks before it plans the form; the launch below cannot decline)
+bool conv3d_sk_applies(int variant, const ConvDesc& d) {
+  const int Ci = d.Ci, Co = d.Co;
+  if (Ci % (2 * SK_NW) != 0 || (Co != 32 && Co != 64) || d.W % 4 != 0 || d.x_align < 16) return false;
+  const int Wo = (d.W - 1) / d.stride + 1;
+  if (Wo % 4 == 0 && (d.y_align < 16 || d.res_align < 16)) return false;
+  if ((long long)(Ci / SK_NW) * d.D * d.H * d.W * 4 >= 0x7fffffffLL) return false;   // 32-bit offsets inside a wave's channels
+  const int NP = Ci / (2 * SK_NW);
+  return sk_visit(variant, d.stride, Co, [&](auto c) {
+           using C = decltype(c);
+           return (NP > C::NPR || sk_lds_bytes<C>(Ci) > 160 * 1024) ? -1 : 0;
+         }) == 0;
+}
+
+int conv3d_sk_launch(int variant, const float* x, const float* wp, const float* scale, const float* shift, const float* res, float* y,
+                     int B, int Ci, int Co, int D, int H, int W, int stride, int relu, hipStream_t st) {
+  const int rc = sk_visit(variant, stride, Co, [&](auto c) {
+    return launch_sk<decltype(c)>(x, wp, scale, shift, res, y, B, Ci, Co, D, H, W, relu, st);
+  });
+  return rc == -1 ? fail(DMB_EUNSUPPORTED, "conv3d: the plan names a split-K variant this build does not hold") : rc;
 }
 
 // The 2-D layers (dmb_conv2d_f32, kernel 3, stride 1, dilation 1 or 2) in the same form: x / y / residual are the channel windows

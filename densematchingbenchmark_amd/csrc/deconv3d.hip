@@ -470,11 +470,6 @@ using DTileCfg = DCfg<0, CO, D_TILE[T].ty, D_TILE[T].tx, 256 / CO, CO / 32, D_TI
 
 using namespace dmb;
 
-static int align_of(const void* p) {   // a pointer enters the plan as its alignment: 1 .. 16 bytes (NULL: 16)
-  const uintptr_t low = (uintptr_t)p & 15;
-  return low ? (int)(low & (~low + 1)) : 16;
-}
-
 extern "C" int dmb_deconv3d_k3s2_plan(int B, int Ci, int Co, int D, int H, int W, int Wout, int x_align, int y_align, int residual_align,
                                       int workspace_align, int single_chain, int ncu) {
   const char* why = "";

@@ -111,9 +111,25 @@ __device__ __forceinline__ int cd_row(int r, int h) { return (r & 3) + 8 * (r >>
 
 #endif  // __HIPCC__
 
-// csrc/conv3d_sk.hip: split-K form of the stride-1 / stride-2 convolution for launches that do not fill the chip; -1 = does not apply.
-int conv3d_sk_try(int variant, const float* x, const float* wp, const float* scale, const float* shift, const float* res, float* y,
-                  int B, int Ci, int Co, int D, int H, int W, int stride, int relu, hipStream_t st);
+// A pointer enters a launch plan as its alignment: 1 .. 16 bytes (NULL: 16)
+inline int align_of(const void* p) {
+  const uintptr_t low = (uintptr_t)p & 15;
+  return low ? (int)(low & (~low + 1)) : 16;
+}
+
+// What dmb_conv3d_k3_f32 decides a launch from (conv3d_plan, conv3d.hip): no pointers, no device.
+struct ConvDesc {
+  int B, Ci, Co, D, H, W, stride;
+  int x_align, y_align, res_align;   // bytes (a power of two; 16 or more = 16-byte aligned; no residual: 16)
+  bool single_chain;                 // DMB_CONV_SINGLE_CHAIN: one fma chain per output whatever the launch's size
+  int ncu;                           // compute units of the device
+};
+
+// csrc/conv3d_sk.hip: split-K form of the stride-1 / stride-2 convolution for launches that do not fill the chip.  conv3d_sk_applies:
+// whether `variant` is built for the launch and takes its shape and alignments (pure); conv3d_sk_launch runs a variant that applies.
+bool conv3d_sk_applies(int variant, const ConvDesc& d);
+int conv3d_sk_launch(int variant, const float* x, const float* wp, const float* scale, const float* shift, const float* res, float* y,
+                     int B, int Ci, int Co, int D, int H, int W, int stride, int relu, hipStream_t st);
 
 int conv2d_sk_try(const float* x, const float* wp, const float* scale, const float* shift, const float* res, float* y, int B, int Ci,
                   int Co, int H, int W, int dilation, int relu, int in_ctot, int out_ctot, int res_ctot, hipStream_t st);

@@ -525,6 +525,28 @@ def zero_columns_(t, x0):
 
 
 DECONV_PLAN_SPLIT_K, DECONV_PLAN_QUEUE, DECONV_PLAN_PARITY = 1, 2, 3   # dmb_deconv3d_k3s2_plan: the form, bits 8.. of a plan code
+# dmb_conv3d_k3_plan: the form, bits 8.. of a plan code
+CONV_PLAN_SPLIT_K, CONV_PLAN_S1_VEC, CONV_PLAN_S1_FLAT, CONV_PLAN_S1_C128, CONV_PLAN_S2 = 1, 2, 3, 4, 5
+
+
+def _align(t):
+    """A tensor's base alignment as the plan queries take it: 1 .. 16 bytes; None (no such operand): 16."""
+    p = 0 if t is None else t.data_ptr()
+    return min(p & -p or 16, 16)
+
+
+def conv3d_k3_plan(x, Co, stride=1, residual=None, out=None, ncu=0):
+    """What ``conv3d_k3(x, wpack, Co, ..., stride=stride, residual=residual, out=out)`` would run under the current small-launch
+    policy (``set_split_k``): the plan code (form << 8) | index of dmb_conv3d_k3_plan (include/dmb_hip.h), or minus the DMB_E* code
+    of a refusal.  ``x`` may be a shape (B, Ci, D, H, W): every operand then counts as 16-byte aligned, as does a fresh output
+    (``out`` None).  ``ncu``: compute units to plan for, 0 = the current device's.  Stride 1 or 2 only."""
+    shape = tuple(x) if isinstance(x, (tuple, list)) else tuple(x.shape)
+    B, Ci, D, H, W = (int(v) for v in shape)
+    xa = 16 if isinstance(x, (tuple, list)) else _align(x)
+    stride = _hw_stride(stride, "conv3d_k3_plan")
+    if stride == "hw":
+        raise _lib.DmbLibraryError("conv3d_k3_plan: stride (1, 2, 2) is dmb_conv3d_k3_hw_f32's, which has one form")
+    return _lib.load().dmb_conv3d_k3_plan(B, Ci, int(Co), D, H, W, int(stride), xa, _align(out), _align(residual), 0 if _split_k else 1, int(ncu))
 
 
 def padded_rows_applicable(x, Co):

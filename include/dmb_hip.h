@@ -44,7 +44,7 @@ extern "C" {
 
 #define DMB_MAX_DISP_SAMPLES 256 /* upper bound on the number of disparity samples D */
 
-/* ABI version: bumped whenever a signature below changes (9: dmb_deconv3d_k3s2_plan added; 8: dmb_bn_train_fwd_f32, dmb_catconv_pack_weights_f32, dmb_conv3d_pack_weights_multi_f32, dmb_cat_first_wgrad_maps_f32, dmb_conv3d_k3_bnstats_f32 and dmb_bn_train_act_f32 added, dmb_bn_act_bwd_f32 takes the gradient its
+/* ABI version: bumped whenever a signature below changes (10: dmb_conv3d_k3_plan added; 9: dmb_deconv3d_k3s2_plan added; 8: dmb_bn_train_fwd_f32, dmb_catconv_pack_weights_f32, dmb_conv3d_pack_weights_multi_f32, dmb_cat_first_wgrad_maps_f32, dmb_conv3d_k3_bnstats_f32 and dmb_bn_train_act_f32 added, dmb_bn_act_bwd_f32 takes the gradient its
  * skip operand already holds (`dres_acc`); 7: DMB_CONV_SINGLE_CHAIN in the `relu` argument of the convolution
  * entry points, `flags` argument of dmb_conv3d_k3_c1_f32; 6: dmb_stereo_pad_normalize_f32 / _u8 added; 5: dmb_fast_fms_bwd_f32 takes a mode, the forward's norm and an
  * optional gradient buffer for per-pixel samples; 4: workspace argument of dmb_deconv3d_k3s2_f32, the merged-heads entry
@@ -222,6 +222,29 @@ int dmb_deconv3d_pack_weights_f32(const float* w, float* wpack, int Ci, int Co, 
 int dmb_conv3d_k3_f32(const float* x, const float* wpack, const float* scale, const float* shift,
                       const float* residual, float* y, int B, int Ci, int Co, int D, int H, int W,
                       int stride, int relu, void* stream);
+/* What dmb_conv3d_k3_f32 would run for a launch, without launching anything or touching a device: a pure function of its
+ * arguments.  Pointers enter as their alignment in bytes (a power of two; 16 or more = 16-byte aligned; 16 for a NULL residual);
+ * single_chain: whether DMB_CONV_SINGLE_CHAIN is set; ncu: the device's compute units, or <= 0 for the current device's (256 where
+ * there is none).  Returns
+ *   (form << 8) | index  with form 1 = split-K over the eight waves of a workgroup (small launches, Co 32 or 64, Ci % 16 == 0, 16-byte
+ *                          rows): index = variant + 4 at stride 2; variant 1 = 16 x 2 output voxels and one 32-channel row tile per
+ *                          workgroup, 3 = 32 x 2 voxels and both row tiles (stride 2, 32 -> 64 only): 0x101, 0x105, 0x107;
+ *                        form 2 = stride 1, 16-byte rows (W % 4 == 0, 16-byte aligned x / y / residual, one batch item of the output
+ *                          below 2 GiB).  32 output channels: index 0 = 48 columns x 4 rows, 1 = 24 x 8, 2 = 32 x 4, 3 = 32 x 2 (four
+ *                          z-slices each; the tile dmb_conv3d_k3_bnstats_f32 takes too); 64 output channels: 4 = runs of 64 voxels of
+ *                          the (y, x) plane in memory order, 5 = 40 x 4, 6 = 24 x 4, 7 = 32 x 4, 8 = 16 x 2 (two z-slices each);
+ *                        form 3 = stride 1, flattened tiles with dword staging (any W, 4-byte aligned operands): index 0 / 1 = 32
+ *                          output channels, 60 / 52 columns x 4 rows x 4 z-slices; 2 / 3 = 64 output channels, 60 / 52 x 4 x 2;
+ *                        form 4 = stride 1, 128 output channels: index 0 (60 columns x 2 rows x 2 z-slices, dword staging);
+ *                        form 5 = stride 2.  64 output channels with 16-byte input rows (W % 4 == 0, 16-byte aligned x), in OUTPUT
+ *                          voxels, two z-slices each: index 0 / 1 / 2 = 30 columns x 1 / 2 / 4 rows with the 8-byte epilogue (8-byte
+ *                          aligned y / residual), 3 = 22 columns x 4 rows, 4 = 30 x 4 with the dword epilogue; dword staging, 30
+ *                          columns x 4 rows: 5 = 64, 6 = 32 (four z-slices), 7 = 128 output channels (one z-slice);
+ *   or -DMB_EINVAL / -DMB_EUNSUPPORTED where the launch would be refused with that code (dmb_last_error() then names the reason).
+ * Every form is ONE k-ordered fma chain per output -- the same bits whatever the tile -- except split-K, which is planned for small
+ * launches only and never under single_chain. */
+int dmb_conv3d_k3_plan(int B, int Ci, int Co, int D, int H, int W, int stride, int x_align, int y_align, int residual_align,
+                       int single_chain, int ncu);
 
 /* Conv3d kernel 3 pad 1 stride 1 with ONE output channel (classifier heads: PSMNet.py:46,50,54,
  * StereoNet.py:39).  w: raw [1, Ci, 3, 3, 3]; bias_host: scalar added to every output; residual may be

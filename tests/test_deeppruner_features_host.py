@@ -136,7 +136,7 @@ def test_entry_point_validates_before_any_device_call():
                        ((p, p, p, p, 1, 1, 1 << 14, 1 << 13), EUNSUPPORTED)):                                              # a 2 GiB output
         assert head(*args, None) == code, args
         assert b"refine_head" in lib.dmb_last_error(), args
-    assert lib.dmb_abi_version() == 9 == _lib.ABI_VERSION
+    assert lib.dmb_abi_version() == 10 == _lib.ABI_VERSION
     del keep
 
 

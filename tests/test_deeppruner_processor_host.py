@@ -151,7 +151,7 @@ def test_entry_points_validate_before_any_device_call():
     for Ci, Co in ((0, 4), (4, 0), (17, 4), (4, 17), (17, 17)):
         assert conv(p, p, p, p, p, 1, Ci, Co, 8, 8, 1, None) == EUNSUPPORTED, (Ci, Co)
         assert b"conv2d_k5_small" in lib.dmb_last_error()
-    assert lib.dmb_abi_version() == 9 == _lib.ABI_VERSION
+    assert lib.dmb_abi_version() == 10 == _lib.ABI_VERSION
     del keep
 
 

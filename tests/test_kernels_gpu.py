@@ -284,26 +284,41 @@ def test_conv3d_k3(dev, Ci, Co, stride, shape):
     assert (got - F.conv3d(x, w, None, stride=stride, padding=1)).abs().max().item() <= 2e-5
 
 
+# Which instantiation each shape below takes on 256 compute units (dmb_conv3d_k3_plan, include/dmb_hip.h; the tile is a cost estimate
+# over workgroup rounds, not a function of the width): launches this small take split-K (0x101 / 0x105), the smallest tile of their
+# list (0x203 = 32 x 2, 0x208 = 16 x 2) or, off the 16-byte rows, the flattened forms; (4, 24, 20, 120) alone fills the chip and takes
+# the 40 x 4 row quads (0x205).  tests/test_conv3d_every_planned_form_gpu.py runs every other tile.
+_ANY_CHANNELS_PLAN = {
+    (5, 32, 1, (1, 4, 6, 50)): 0x301, (40, 64, 1, (1, 3, 5, 48)): 0x208, (24, 32, 1, (2, 5, 7, 96)): 0x203,
+    (12, 32, 2, (1, 6, 9, 21)): 0x506, (7, 64, 2, (1, 5, 8, 33)): 0x505, (32, 32, 1, (1, 3, 6, 156)): 0x101,
+    (64, 64, 1, (1, 5, 9, 80)): 0x101, (20, 64, 1, (2, 3, 6, 120)): 0x208, (64, 64, 1, (1, 2, 3, 40)): 0x101,
+    (64, 64, 1, (1, 4, 7, 72)): 0x101, (64, 64, 1, (4, 24, 20, 120)): 0x205, (64, 64, 1, (1, 4, 9, 60)): 0x101,
+    (32, 32, 1, (2, 5, 7, 128)): 0x101, (64, 32, 1, (1, 4, 6, 64)): 0x101, (64, 64, 1, (1, 5, 9, 64)): 0x101,
+    (32, 64, 1, (2, 4, 8, 32)): 0x101, (32, 64, 2, (1, 6, 8, 128)): 0x105, (64, 64, 2, (2, 4, 9, 64)): 0x105,
+    (64, 64, 2, (1, 4, 8, 240)): 0x105,
+}
+
+
 @pytest.mark.parametrize("Ci,Co,stride,shape", [
     (5, 32, 1, (1, 4, 6, 50)),      # odd channel count: zero-padded weight fragments + bounds-checked copies
-    (40, 64, 1, (1, 3, 5, 48)),     # row-pair width with 64 output channels -> flattened path
-    (24, 32, 1, (2, 5, 7, 96)),     # W % 48 == 0 -> row-pair tiles
+    (40, 64, 1, (1, 3, 5, 48)),
+    (24, 32, 1, (2, 5, 7, 96)),
     (12, 32, 2, (1, 6, 9, 21)),
     (7, 64, 2, (1, 5, 8, 33)),
-    (32, 32, 1, (1, 3, 6, 156)),    # StereoNet width: TX = 52 tiles
-    (64, 64, 1, (1, 5, 9, 80)),     # W % 40 == 0 with 64 output channels -> row-quad tiles (8 columns x 4 rows)
+    (32, 32, 1, (1, 3, 6, 156)),    # StereoNet width
+    (64, 64, 1, (1, 5, 9, 80)),
     (20, 64, 1, (2, 3, 6, 120)),
     (64, 64, 1, (1, 2, 3, 40)),
-    (64, 64, 1, (1, 4, 7, 72)),     # W % 24 == 0 only -> 24-column row-quad tiles
-    (64, 64, 1, (4, 24, 20, 120)),  # both widths possible: picked by the rounds x columns model
-    (64, 64, 1, (1, 4, 9, 60)),     # few tiles, W % 30 == 0 -> 30-column flattened tiles
-    (32, 32, 1, (2, 5, 7, 128)),    # training-crop widths: 32-column row-pair tiles ...
+    (64, 64, 1, (1, 4, 7, 72)),
+    (64, 64, 1, (4, 24, 20, 120)),  # fills the chip: picked by the rounds x columns model
+    (64, 64, 1, (1, 4, 9, 60)),
+    (32, 32, 1, (2, 5, 7, 128)),    # training-crop widths
     (64, 32, 1, (1, 4, 6, 64)),
-    (64, 64, 1, (1, 5, 9, 64)),     # ... and 32-column row-quad tiles
+    (64, 64, 1, (1, 5, 9, 64)),
     (32, 64, 1, (2, 4, 8, 32)),
-    (32, 64, 2, (1, 6, 8, 128)),    # stride 2 at crop widths: 22-column tiles
+    (32, 64, 2, (1, 6, 8, 128)),    # stride 2 at crop widths
     (64, 64, 2, (2, 4, 9, 64)),
-    (64, 64, 2, (1, 4, 8, 240)),    # ... and the 30-column ones
+    (64, 64, 2, (1, 4, 8, 240)),
 ])
 def test_conv3d_any_channels(dev, Ci, Co, stride, shape):
     ops = _ops()
@@ -312,6 +327,7 @@ def test_conv3d_any_channels(dev, Ci, Co, stride, shape):
     w = _rand((Co, Ci, 3, 3, 3), 32, 1.0 / math.sqrt(Ci * 27))
     sc, sh = _affine(Co, 33)
     ref = F.conv3d(x, w, None, stride=stride, padding=1) * sc.view(1, -1, 1, 1, 1) + sh.view(1, -1, 1, 1, 1)
+    assert ops.conv3d_k3_plan(x.to(dev), Co, stride) == _ANY_CHANNELS_PLAN[(Ci, Co, stride, shape)]
     wp = ops.pack_conv3d_weights(w.to(dev))
     got = ops.conv3d_k3(x.to(dev), wp, Co, sc.to(dev), sh.to(dev), None, stride, True).cpu()
     assert (got - F.relu(ref)).abs().max().item() <= 2e-5
@@ -856,7 +872,11 @@ def test_conv3d_s2_pair_epilogue_is_bit_identical(dev, Ci, shape, mode):
         ref = F.relu(ref) + res
     wp = ops.pack_conv3d_weights(w.to(dev))
     outs = []
-    for out in (None, _misaligned(torch.zeros(B, 64, Do, Ho, Wo), dev)):
+    # the plans of the two launches: one-row tiles with the 8-byte epilogue (0x500) for the aligned output; for the 4-byte aligned
+    # one the four-row tile with the dword epilogue (0x504) -- or, at Wo = 62, the 22-column tile (0x503), dword epilogue as well
+    plans = (0x500, 0x503 if shape == (1, 4, 4, 124) else 0x504)
+    for out, plan in zip((None, _misaligned(torch.zeros(B, 64, Do, Ho, Wo), dev)), plans):
+        assert ops.conv3d_k3_plan(x.to(dev), 64, 2, None if res is None else res.to(dev), out) == plan
         outs.append(ops.conv3d_k3(x.to(dev), wp, 64, sc.to(dev), sh.to(dev), None if res is None else res.to(dev), 2, relu, out=out))
     assert torch.equal(outs[0], outs[1])
     assert (outs[0].cpu() - ref).abs().max().item() <= 2e-5
