@@ -2,8 +2,9 @@
 
 PyTorch is plumbing here: it owns device memory (``tensor.data_ptr()``) and the current HIP stream
 (``torch.cuda.current_stream().cuda_stream``); everything that computes lives behind the C ABI of
-``include/dmb_hip.h``.  There is NO fallback: if the library is missing or a tensor is not a CUDA/HIP
-tensor, the call raises.
+``include/dmb_hip.h``.  That header is the only statement of the ABI: the ctypes table (``SIGNATURES``), the ABI version and the
+``DMB_*`` constants are read from it at import, and ``launch`` marshals every call from the parsed prototype.  There is NO
+fallback: if the library is missing or a tensor is not a CUDA/HIP tensor, the call raises.
 """
 import ctypes
 import os
@@ -15,130 +16,68 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # DMB_LIB=dev (development scripts only): the build with the kernel-variant switches, lib/libdmb_hip_dev.so (build.py dev=True)
 DEV_BUILD = os.environ.get("DMB_LIB", "").startswith("dev")    # "dev" or "dev_<tag>" (a build-time experiment, build.py)
 LIB_PATH = os.path.join(_PKG, "lib", "libdmb_hip_%s.so" % os.environ["DMB_LIB"] if DEV_BUILD else "libdmb_hip.so")
-DECONV3D_WORKSPACE_BYTES = 2048   # include/dmb_hip.h: DMB_DECONV3D_WORKSPACE_BYTES
-CONV_SINGLE_CHAIN = 0x100         # include/dmb_hip.h: DMB_CONV_SINGLE_CHAIN
-CONV3D_HEAD_PACKED_FLOATS = 1024  # include/dmb_hip.h: DMB_CONV3D_HEAD_PACKED_FLOATS
-DEEPPRUNER_LOSS_WORKSPACE_DOUBLES = 9216   # include/dmb_hip.h: DMB_DEEPPRUNER_LOSS_WORKSPACE_DOUBLES
 HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "dmb_hip.h")
 
-_c_int, _c_float, _c_void_p, _c_ll, _c_double = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_double
-_P = _c_void_p  # device pointer
+
+class DmbLibraryError(RuntimeError):
+    pass
+
+
+# ---------------------------------------------------------------------------------------------- the header is the table
 _HI = ctypes.POINTER(ctypes.c_int)  # host int array
 _HF = ctypes.POINTER(ctypes.c_float)  # host float array
+_SCALARS = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float, "double": ctypes.c_double}
+_POINTEES = ("void", "float", "double", "int", "long long", "unsigned char")   # what a device pointer may point at
 
-ABI_VERSION = 10
 
-# name -> (restype, argtypes)
-SIGNATURES = {
-    "dmb_abi_version": (_c_int, []),
-    "dmb_last_error": (ctypes.c_char_p, []),
-    "dmb_build_id": (ctypes.c_char_p, []),
-    "dmb_cat_fms_f32": (_c_int, [_P, _P, _P, _c_int, _c_int, _c_int, _c_int, _c_int, _HI, _P]),
-    "dmb_dif_fms_f32": (_c_int, [_P, _P, _P, _c_int, _c_int, _c_int, _c_int, _c_int, _HI, _P]),
-    "dmb_gwc_fms_f32": (_c_int, [_P, _P, _P, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _HI, _c_int, _c_int, _P]),
-    "dmb_fast_cat_fms_f32": (_c_int, [_P, _P, _P, _P] + [_c_int] * 6 + [_P]),
-    "dmb_fast_dif_fms_f32": (_c_int, [_P, _P, _P, _P] + [_c_int] * 7 + [_c_float, _P]),
-    "dmb_fast_fms_bwd_f32": (_c_int, [_P] * 9 + [_c_int] * 7 + [_c_float, _P]),
-    "dmb_spn_gaterecurrent2d_f32": (_c_int, [_P] * 5 + [_c_int] * 6 + [_P]),
-    "dmb_spn_gaterecurrent2d_bwd_f32": (_c_int, [_P] * 10 + [_c_int] * 6 + [_P]),
-    "dmb_conv2d_k3_multi_f32": (_c_int, [_c_int, _P, _P, _P, _P, _P, _c_int, _c_int, _c_int, _c_int, _P]),
-    "dmb_cat_fms_into_f32": (_c_int, [_P, _P, _P, _c_int, _c_int, _c_int, _c_int, _c_int, _HI, _c_int, _c_int, _P]),
-    "dmb_correlation1d_f32": (_c_int, [_P, _P, _P, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _P]),
-    "dmb_copy_window_f32": (_c_int, [_P, _P, _c_ll, _c_int, _c_int, _c_int, _P]),
-    "dmb_catconv_pack_weights_f32": (_c_int, [_P, _P, _c_int, _c_int, _c_int, _c_int, _P]),
-    "dmb_catconv_finalize_f32": (_c_int, [_P] * 8 + [_c_int] * 8 + [_P]),
-    "dmb_catconv_combine_f32": (_c_int, [_P] * 9 + [_c_int] * 7 + [_P]),
-    "dmb_conv3d_packed_floats": (_c_ll, [_c_int, _c_int]),
-    "dmb_deconv3d_packed_floats": (_c_ll, [_c_int, _c_int]),
-    "dmb_conv3d_pack_weights_f32": (_c_int, [_P, _P, _c_int, _c_int, _P]),
-    "dmb_deconv3d_pack_weights_f32": (_c_int, [_P, _P, _c_int, _c_int, _P]),
-    "dmb_conv3d_k3_f32": (_c_int, [_P, _P, _P, _P, _P, _P] + [_c_int] * 8 + [_P]),
-    "dmb_conv3d_k3_c1_f32": (_c_int, [_P, _P, _c_float, _P, _P] + [_c_int] * 6 + [_P]),
-    "dmb_conv3d_k3_head_workspace_floats": (_c_ll, [_c_int] * 4),
-    "dmb_conv3d_k3_head_preferred": (_c_int, [_c_int] * 4),
-    "dmb_conv3d_head_pack_weights_f32": (_c_int, [_P, _P, _P]),
-    "dmb_conv3d_k3_head_f32": (_c_int, [_P] * 5 + [_c_float, _P, _P, _P] + [_c_int] * 6 + [_P]),
-    "dmb_deconv3d_k3s2_f32": (_c_int, [_P, _P, _P, _P, _P, _P] + [_c_int] * 8 + [_P, _P]),
-    "dmb_deconv3d_k3s2_plan": (_c_int, [_c_int] * 13),
-    "dmb_conv3d_k3_plan": (_c_int, [_c_int] * 12),
-    "dmb_conv3d_k3_hw_f32": (_c_int, [_P, _P, _P, _P, _P, _P] + [_c_int] * 8 + [_P]),
-    "dmb_deconv3d_k3_hw_f32": (_c_int, [_P, _P, _P, _P, _P, _P] + [_c_int] * 7 + [_P]),
-    "dmb_zero_columns_f32": (_c_int, [_P, _c_ll, _c_int, _c_int, _P]),
-    "dmb_trilinear_ac_f32": (_c_int, [_P, _P] + [_c_int] * 7 + [_P]),
-    "dmb_deconv3d_k8s4_c1_f32": (_c_int, [_P, _P, _P] + [_c_int] * 4 + [_P]),
-    "dmb_deconv3d_k8s4_c1_soft_argmin_f32": (_c_int, [_P, _P, _P, _P] + [_c_int] * 4 + [_c_float, _HF, _P]),
-    "dmb_soft_argmin_f32": (_c_int, [_P, _P, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _HF, _P]),
-    "dmb_soft_argmin_sampled_f32": (_c_int, [_P, _P, _P, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _P]),
-    "dmb_local_soft_argmin_f32": (_c_int, [_P, _P, _P] + [_c_int] * 8 + [_c_float, _P]),
-    "dmb_trilinear_soft_argmin_f32": (_c_int, [_P, _P] + [_c_int] * 7 + [_c_float, _HF, _P]),
-    "dmb_trilinear_ac_soft_argmin_f32": (_c_int, [_P, _P, _P] + [_c_int] * 7 + [_c_float, _HF, _P]),
-    "dmb_conf_head_packed_floats": (_c_ll, [_c_int, _c_int]),
-    "dmb_conf_head_pack_weights_f32": (_c_int, [_P, _P, _c_int, _c_int, _P]),
-    "dmb_conf_head_f32": (_c_int, [_P, _P, _P, _P, _P, _P] + [_c_int] * 5 + [_P]),
-    "dmb_conf_gather_f32": (_c_int, [_P, _P, _P] + [_c_int] * 4 + [_P]),
-    "dmb_conf_phase_conv2d_f32": (_c_int, [_P] * 6 + [_c_int] * 5 + [_P]),
-    "dmb_conf_ring_f32": (_c_int, [_P] * 6 + [_c_int] * 5 + [_P]),
-    "dmb_conv2d_packed_floats": (_c_ll, [_c_int, _c_int, _c_int]),
-    "dmb_conv2d_pack_weights_f32": (_c_int, [_P, _P, _c_int, _c_int, _c_int, _P]),
-    "dmb_conv2d_f32": (_c_int, [_P, _P, _P, _P, _P, _P] + [_c_int] * 12 + [_P]),
-    "dmb_avgpool2d_f32": (_c_int, [_P, _P] + [_c_int] * 7 + [_P]),
-    "dmb_bilinear_ac_f32": (_c_int, [_P, _P] + [_c_int] * 8 + [_P]),
-    "dmb_bilinear_scale_f32": (_c_int, [_P, _P] + [_c_int] * 6 + [_c_float] + [_c_int] * 2 + [_P]),
-    "dmb_epe_accum_f64": (_c_int, [_P, _P, _P, _P] + [_c_int] * 5 + [_c_float, _c_float, _P]),
-    "dmb_epe_accum_multi_f64": (_c_int, [_c_int, _P, _P, _P, _P] + [_c_int] * 5 + [_c_float, _c_float, _P]),
-    "dmb_conv3d_x6_packed_bytes": (_c_ll, [_c_int, _c_int]),
-    "dmb_conv3d_x6_pack_weights_f32": (_c_int, [_P, _P, _c_int, _c_int, _P]),
-    "dmb_conv3d_k3_x6_f32": (_c_int, [_P, _P, _P, _P, _P, _P] + [_c_int] * 7 + [_P]),
-    "dmb_conv3d_pack_dgrad_weights_f32": (_c_int, [_P, _P, _c_int, _c_int, _P]),
-    "dmb_conv3d_wgrad_workspace_floats": (_c_ll, [_c_int, _c_int]),
-    "dmb_conv3d_k3_wgrad_f32": (_c_int, [_P, _P, _P, _P] + [_c_int] * 6 + [_P]),
-    "dmb_conv3d_k3s2_wgrad_f32": (_c_int, [_P, _P, _P, _P] + [_c_int] * 9 + [_P]),
-    "dmb_conv2d_wgrad_workspace_floats": (_c_ll, [_c_int, _c_int]),
-    "dmb_conv2d_wgrad_f32": (_c_int, [_P, _P, _P, _P] + [_c_int] * 7 + [_P]),
-    "dmb_channel_dot_f32": (_c_int, [_P, _P, _P, _P, _c_int, _c_int, _c_ll, _P]),
-    "dmb_conv3d_pack_weights_multi_f32": (_c_int, [_P, _c_int, _P]),
-    "dmb_cat_first_wgrad_maps_f32": (_c_int, [_P, _P, _P, _c_int, _c_int, _c_int, _c_int, _c_int, _P]),
-    "dmb_conv3d_k3_bnstats_partials": (_c_ll, [_c_int] * 6),
-    "dmb_conv3d_k3_bnstats_f32": (_c_int, [_P] * 4 + [_c_int] * 6 + [_P]),
-    "dmb_bn_train_act_f32": (_c_int, [_P, _P, _c_int] + [_P] * 5 + [_c_float, _c_float] + [_P] * 6 + [_c_int, _c_int, _c_ll, _c_int, _P]),
-    "dmb_bn_workspace_doubles": (_c_ll, [_c_int, _c_ll]),
-    "dmb_bn_train_stats_f32": (_c_int, [_P, _P, _P, _P, _P, _c_float, _c_float, _P, _P, _P, _P, _P, _c_int, _c_int, _c_ll, _P]),
-    "dmb_bn_act_f32": (_c_int, [_P, _P, _P, _P, _P, _c_int, _c_int, _c_ll, _c_int, _P]),
-    "dmb_bn_train_fwd_f32": (_c_int, [_P] * 6 + [_c_float, _c_float] + [_P] * 7 + [_c_int, _c_int, _c_ll, _c_int, _P]),
-    "dmb_bn_act_bwd_f32": (_c_int, [_P] * 13 + [_c_int, _c_int, _c_ll, _c_int, _c_int, _P]),
-    "dmb_cat_fms_bwd_f32": (_c_int, [_P, _P, _P, _c_int, _c_int, _c_int, _c_int, _c_int, _HI, _P]),
-    "dmb_dif_fms_bwd_f32": (_c_int, [_P, _P, _P, _c_int, _c_int, _c_int, _c_int, _c_int, _HI, _P]),
-    "dmb_soft_argmin_bwd_f32": (_c_int, [_P, _P, _P, _P, _c_int, _c_int, _c_int, _c_int, _c_float, _HF, _P]),
-    "dmb_trilinear_ac_soft_argmin_bwd_f32": (_c_int, [_P, _P, _P, _P, _P, _P] + [_c_int] * 7 + [_c_float, _HF, _P]),
-    "dmb_trilinear_ac_bwd_f32": (_c_int, [_P, _P, _P] + [_c_int] * 7 + [_P]),
-    "dmb_avgpool2d_bwd_f32": (_c_int, [_P, _P] + [_c_int] * 5 + [_P]),
-    "dmb_bilinear_ac_bwd_f32": (_c_int, [_P, _P] + [_c_int] * 6 + [_P]),
-    "dmb_bilinear_scale_bwd_f32": (_c_int, [_P, _P] + [_c_int] * 6 + [_c_float, _P]),
-    "dmb_deconv3d_k8s4_bwd_workspace_doubles": (_c_ll, []),
-    "dmb_deconv3d_k8s4_c1_bwd_f32": (_c_int, [_P] * 6 + [_c_int] * 4 + [_P]),
-    "dmb_loss_workspace_doubles": (_c_ll, [_c_ll]),
-    "dmb_stereo_focal_loss_fwd_f32": (_c_int, [_P, _P, _P, _c_float, _HF, _P, _P, _P] + [_c_int] * 4 + [_c_float] * 5 + [_P]),
-    "dmb_stereo_focal_loss_bwd_f32": (_c_int, [_P, _P, _P, _c_float, _HF, _P, _P, _P, _c_float, _P, _P] + [_c_int] * 4
-                                      + [_c_float] * 5 + [_P]),
-    "dmb_map_loss_fwd_f32": (_c_int, [_P, _P, _P, _P, _c_ll, _c_float, _c_float, _c_int, _P]),
-    "dmb_stereo_pad_normalize_f32": (_c_int, [_P, _P] + [_c_int] * 11 + [_HF, _HF, _P]),
-    "dmb_stereo_pad_normalize_u8": (_c_int, [_P, _P] + [_c_int] * 11 + [_HF, _HF, _P]),
-    "dmb_map_loss_bwd_f32": (_c_int, [_P, _P, _P, _P, _c_float, _P, _c_ll, _c_float, _c_float, _c_int, _P]),
-    "dmb_preact_conv_f32": (_c_int, [_P, _P, _c_int] + [_P] * 9 + [_c_int] * 13 + [_P]),
-    "dmb_anynet_stage_samples_f32": (_c_int, [_P] * 4 + [_c_int] * 6 + [_c_float, _P]),
-    "dmb_add_f32": (_c_int, [_P, _P, _P, _c_ll, _P]),
-    "dmb_anynet_final_maps_f32": (_c_int, [_P] * 4 + [_HI, _HI, _P] + [_c_int] * 3 + [_P]),
-    "dmb_patch_match_step_f32": (_c_int, [_P] * 5 + [_c_float, _c_float, _P, _P] + [_c_int] * 6 + [_c_float] + [_c_int] * 3 + [_P]),
-    "dmb_deeppruner_uniform_samples_f32": (_c_int, [_P, _P, _P] + [_c_int] * 5 + [_c_float, _P]),
-    "dmb_deeppruner_volume_f32": (_c_int, [_P] * 6 + [_c_int] * 6 + [_P]),
-    "dmb_conv2d_k5_small_f32": (_c_int, [_P] * 5 + [_c_int] * 6 + [_P]),
-    "dmb_refine_head_up2_f32": (_c_int, [_P] * 4 + [_c_int] * 4 + [_P]),
-    "dmb_deeppruner_final_maps_f32": (_c_int, [_P] * 3 + [_HI, _HI] + [_P] * 3 + [_c_int] * 6 + [_P]),
-    "dmb_deeppruner_loss_fwd_f32": (_c_int, [_P] * 3 + [_HI, _HI] + [_P] * 6 + [_c_int] * 6 + [_c_float] * 4 + [_c_double, _P]),
-    "dmb_deeppruner_loss_bwd_f32": (_c_int, [_P] * 3 + [_HI, _HI] + [_P] * 10 + [_c_int] * 6 + [_c_float] * 4 + [_c_double, _P]),
-    "dmb_quantile_loss_fwd_f32": (_c_int, [_P] * 6 + [_c_int] * 3 + [_c_float] * 2 + [_c_double, _P]),
-    "dmb_quantile_loss_bwd_f32": (_c_int, [_P] * 7 + [_c_int] * 3 + [_c_float] * 2 + [_c_double, _P]),
-}
+def _ctype(ctype, name, decl):
+    """The ctypes type of one C type of the header; ``name``: the parameter's (None: a return type)."""
+    words = [w for w in ctype.replace("*", " * ").split() if w != "const"]
+    base, stars = " ".join(w for w in words if w != "*"), words.count("*")
+    if stars == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    if stars == 1 and base == "char":
+        return ctypes.c_char_p
+    if name is not None and name.endswith("_host"):     # a HOST array (dmb_hip.h, boundary rules)
+        if stars == 1 and base in ("int", "float"):
+            return _HI if base == "int" else _HF
+    elif stars and name is not None and base in _POINTEES:
+        return ctypes.c_void_p      # a device pointer, a host array of device pointers, the stream
+    raise DmbLibraryError("include/dmb_hip.h: no ctypes type for `%s` in `%s`" % (" ".join((ctype + " " + (name or "")).split()), decl))
+
+
+def parse_header(text):
+    """``(prototypes, defines)`` of the text of include/dmb_hip.h: entry point -> (restype, [(ctype, parameter name), ...]) and
+    DMB_* -> int for every integer ``#define``.  A ``dmb_*`` declaration it cannot map raises -- none is skipped."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    defines = {m.group(1): int(m.group(2), 0)
+               for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(DMB_\w+)[ \t]+(0[xX][0-9a-fA-F]+|\d+)[ \t]*$", text, flags=re.M)}
+    text = re.sub(r'^[ \t]*#.*$|extern\s+"C"\s*\{', " ", text, flags=re.M)
+    text = re.sub(r"typedef\s+struct\s*\{.*?\}\s*\w+\s*;", " ", text, flags=re.S)
+    protos = {}
+    for decl in (" ".join(d.split()) for d in text.split(";")):
+        if not re.search(r"\bdmb_\w+\s*\(", decl):
+            continue
+        m = re.fullmatch(r"([\w \*]+?)\s*\b(dmb_\w+)\s*\(([^()]*)\)", decl)
+        if m is None:
+            raise DmbLibraryError("include/dmb_hip.h: cannot parse the declaration `%s`" % decl)
+        params = []
+        for p in ([] if m.group(3).strip() in ("", "void") else m.group(3).split(",")):
+            pm = re.fullmatch(r"\s*(.*?[\s\*])(\w+)\s*", p)
+            if pm is None:
+                raise DmbLibraryError("include/dmb_hip.h: cannot parse the parameter `%s` of `%s`" % (p.strip(), decl))
+            params.append((_ctype(pm.group(1), pm.group(2), decl), pm.group(2)))
+        protos[m.group(2)] = (_ctype(m.group(1), None, decl), params)
+    return protos, defines
+
+
+PROTOTYPES, DEFINES = parse_header(open(HEADER_PATH).read())
+SIGNATURES = {name: (res, [t for t, _ in params]) for name, (res, params) in PROTOTYPES.items()}   # name -> (restype, argtypes)
+ABI_VERSION = DEFINES["DMB_ABI_VERSION"]
+DECONV3D_WORKSPACE_BYTES = DEFINES["DMB_DECONV3D_WORKSPACE_BYTES"]
+CONV_SINGLE_CHAIN = DEFINES["DMB_CONV_SINGLE_CHAIN"]
+CONV3D_HEAD_PACKED_FLOATS = DEFINES["DMB_CONV3D_HEAD_PACKED_FLOATS"]
+DEEPPRUNER_LOSS_WORKSPACE_DOUBLES = DEFINES["DMB_DEEPPRUNER_LOSS_WORKSPACE_DOUBLES"]
 
 
 def header_symbols():
@@ -146,10 +85,6 @@ def header_symbols():
     text = open(HEADER_PATH).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(dmb_[a-z0-9_]+)\s*\(", text)))
-
-
-class DmbLibraryError(RuntimeError):
-    pass
 
 
 _lib = None
@@ -181,7 +116,7 @@ def load():
                                   "rebuild it (python -m densematchingbenchmark_amd.build)" % (LIB_PATH, got[:12], want[:12]))
     if DEV_BUILD:
         lib.dmb_dev_set_option.restype = None
-        lib.dmb_dev_set_option.argtypes = [_c_int, _c_int]
+        lib.dmb_dev_set_option.argtypes = [ctypes.c_int, ctypes.c_int]
     _lib = lib
     return lib
 
@@ -193,9 +128,9 @@ _shim_state = "untried"      # "untried" | "loaded" | the reason it is not in us
 def shim():
     """The thin torch extension over the same C ABI (csrc/torch_shim.cpp -> lib/_dmb_torch_shim.so: unwraps tensors, takes the
     current HIP stream from c10, raises DmbLibraryError on a non-zero code) for the entry points on the per-pair launch path, or
-    None -- then the ctypes table above binds them, as it binds every other entry point: the SAME functions of the SAME library,
-    only more interpreter time per launch (profiles/r06_binding_overhead.log).  Refused (-> None) unless it was built from the
-    csrc/torch_shim.cpp / dmb_hip.h / torch next to it and linked against the library that is loaded.  DMB_SHIM=0: never;
+    None -- then ``launch`` below calls them through ctypes, as it calls every other entry point: the SAME functions of the SAME
+    library, only more interpreter time per launch (profiles/r06_binding_overhead.log).  Refused (-> None) unless it was built from
+    the csrc/torch_shim.cpp / dmb_hip.h / torch next to it and linked against the library that is loaded.  DMB_SHIM=0: never;
     DMB_SHIM=require: raise instead of returning None."""
     global _shim, _shim_state
     if _shim_state != "untried":
@@ -239,8 +174,9 @@ def check(code, what):
         raise DmbLibraryError("%s failed with code %d (%s)" % (what, code, msg.decode() if msg else ""))
 
 
-def dev_ptr(t, name="tensor", allow_none=False):
-    """Device pointer of a contiguous FP32 HIP tensor; raises for anything else (no silent CPU path)."""
+def dev_ptr(t, name="tensor", allow_none=False, current=None):
+    """Device pointer of a contiguous FP32 HIP tensor; raises for anything else (no silent CPU path).  ``current``: the current
+    device's index where the caller has asked for it already (``launch``: once per call, not once per operand)."""
     if t is None:
         if allow_none:
             return None
@@ -254,7 +190,7 @@ def dev_ptr(t, name="tensor", allow_none=False):
         raise DmbLibraryError("%s has dtype %s; FP32 expected" % (name, t.dtype))
     if not t.is_contiguous():
         raise DmbLibraryError("%s must be contiguous" % name)
-    if t.device.index != torch.cuda.current_device():   # every operand, not only the one the stream is taken from
+    if t.device.index != (torch.cuda.current_device() if current is None else current):   # every operand, not only the stream's
         raise DmbLibraryError("%s lives on cuda:%d but the current device is cuda:%d" % (name, t.device.index, torch.cuda.current_device()))
     return ctypes.c_void_p(t.data_ptr())
 
@@ -276,3 +212,76 @@ def host_ints(values):
 def host_floats(values):
     arr = (ctypes.c_float * len(values))(*[float(v) for v in values])
     return arr
+
+
+# ---------------------------------------------------------------------------------------------- one launch call
+class _Absent:
+    """``opt(None)``: the NULL a call site passes for an optional operand it leaves out."""
+
+    def __repr__(self):
+        return "NULL"
+
+
+NULL = _Absent()
+
+
+def opt(operand):
+    """Marks an OPTIONAL operand at a ``launch`` call site: None goes to the kernel as NULL.  A bare None is refused there."""
+    return NULL if operand is None else operand
+
+
+def _host_slot(label, array):
+    def convert(a):
+        if a is NULL:
+            return None
+        if a is None:
+            raise DmbLibraryError("%s is None" % label)
+        return a if isinstance(a, ctypes.Array) else array(a)
+    return convert
+
+
+def _slot(ctype, label):
+    if ctype is ctypes.c_void_p:
+        return None, label      # a device pointer: ``launch`` hands it to dev_ptr under this name
+    if ctype in (_HI, _HF):
+        return _host_slot(label, host_ints if ctype is _HI else host_floats), label
+    return (int if ctype in (ctypes.c_int, ctypes.c_longlong) else float), label
+
+
+# entry point -> (converter, "entry point: parameter") per argument before `stream`, for the entry points that take one (built once, here)
+_LAUNCH = {name: tuple(_slot(t, "%s: %s" % (name, p)) for t, p in params[:-1])
+           for name, (_, params) in PROTOTYPES.items() if params and params[-1] == (ctypes.c_void_p, "stream")}
+
+
+def launch(name, *args, device=None):
+    """Enqueue the entry point ``name`` on the current stream: ``args`` are its arguments in the header's order without the stream,
+    converted by the header's types --
+      a device pointer takes a tensor (``dev_ptr``'s checks, the error names the C parameter) or, untouched, a ctypes pointer or
+        array (a channel window of a tensor, a host array of device pointers, a table);
+      a ``*_host`` array takes a sequence of numbers (or a ctypes array);
+      ``int`` / ``long long`` and ``float`` / ``double`` go through int() and float();
+      ``opt(x)`` where the operand may be absent: None is then NULL.  A bare None raises, before anything is launched.
+    The stream is the current one of the first tensor's device -- ``dev_ptr`` refuses every operand that is not on the current
+    device, so any tensor names the same stream -- or of ``device`` where it is given (no tensor among the operands).  A non-zero
+    return code raises DmbLibraryError with the library's last error."""
+    slots = _LAUNCH.get(name)
+    if slots is None:
+        raise DmbLibraryError("%s is not an entry point of include/dmb_hip.h that takes a stream" % name)
+    if len(args) != len(slots):
+        raise DmbLibraryError("%s takes %d arguments before the stream, got %d" % (name, len(slots), len(args)))
+    out, current = [], None
+    for (convert, label), a in zip(slots, args):
+        if convert is not None:             # int, float, or a host array's converter
+            a = convert(a)
+        elif a is NULL:
+            a = None
+        elif not isinstance(a, (ctypes.c_void_p, ctypes.Array)):    # those: a channel window, an array of device pointers, a table
+            if current is None and isinstance(a, torch.Tensor) and a.is_cuda:
+                current = torch.cuda.current_device()
+                if device is None:
+                    device = a.device
+            a = dev_ptr(a, label, current=current)
+        out.append(a)
+    if device is None:
+        raise DmbLibraryError("%s: no tensor among the operands and no device= to take the stream from" % name)
+    check(getattr(load(), name)(*out, stream_ptr(device)), name)

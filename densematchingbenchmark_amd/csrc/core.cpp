@@ -45,5 +45,5 @@ extern "C" void dmb_dev_set_option(int key, int value) {
 }
 #endif
 
-extern "C" int dmb_abi_version(void) { return 10; }
+extern "C" int dmb_abi_version(void) { return DMB_ABI_VERSION; }
 extern "C" const char* dmb_last_error(void) { return dmb::g_last_error; }

@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from . import _lib, param_state
-from ._lib import check, dev_ptr, host_floats, host_ints, stream_ptr
+from ._lib import check, dev_ptr, host_floats, host_ints, launch, opt, stream_ptr  # noqa: F401  (re-exported: tests and scripts)
 from .param_state import bump_param_epoch, param_epoch  # noqa: F401  (the names INTEGRATION.md points users at)
 
 
@@ -106,24 +106,20 @@ def _affine_ok(scale, shift, Co, what):
 
 # ---------------------------------------------------------------------------------------------- volumes
 def cat_fms(left, right, disp_idx):
-    lib = _lib.load()
     left, right = _feature_pair(left, right, "cat_fms")
     B, C, H, W = left.shape
     D = len(disp_idx)
     out = torch.empty((B, 2 * C, D, H, W), dtype=torch.float32, device=left.device)
-    check(lib.dmb_cat_fms_f32(dev_ptr(left), dev_ptr(right), dev_ptr(out), B, C, H, W, D, host_ints(disp_idx),
-                              stream_ptr(left.device)), "dmb_cat_fms_f32")
+    launch("dmb_cat_fms_f32", left, right, out, B, C, H, W, D, disp_idx)
     return out
 
 
 def dif_fms(left, right, disp_idx):
-    lib = _lib.load()
     left, right = _feature_pair(left, right, "dif_fms")
     B, C, H, W = left.shape
     D = len(disp_idx)
     out = torch.empty((B, C, D, H, W), dtype=torch.float32, device=left.device)
-    check(lib.dmb_dif_fms_f32(dev_ptr(left), dev_ptr(right), dev_ptr(out), B, C, H, W, D, host_ints(disp_idx),
-                              stream_ptr(left.device)), "dmb_dif_fms_f32")
+    launch("dmb_dif_fms_f32", left, right, out, B, C, H, W, D, disp_idx)
     return out
 
 
@@ -146,26 +142,22 @@ def _fast_samples(left, disp_sample):
 
 def fast_cat_fms(left, right, disp_sample):
     """cat_fms.py:51-82 on csrc/warp_volume.hip: [B, C, H, W] x 2, samples [D] or [B, D, H, W] -> [B, 2C, D, H, W]."""
-    lib = _lib.load()
     left, right = _feature_pair(left, right, "fast_cat_fms")
     B, C, H, W = left.shape
     ds, D, per_pixel = _fast_samples(left, disp_sample)
     out = torch.empty((B, 2 * C, D, H, W), dtype=torch.float32, device=left.device)
-    check(lib.dmb_fast_cat_fms_f32(dev_ptr(left), dev_ptr(right), dev_ptr(ds), dev_ptr(out), B, C, D, H, W, per_pixel,
-                                   stream_ptr(left.device)), "dmb_fast_cat_fms_f32")
+    launch("dmb_fast_cat_fms_f32", left, right, ds, out, B, C, D, H, W, per_pixel)
     return out
 
 
 def fast_dif_fms(left, right, disp_sample, normalize=False, p=1.0):
     """dif_fms.py:49-86: -> [B, C, D, H, W], or [B, D, H, W] (p-norm over the channels) with ``normalize``."""
-    lib = _lib.load()
     left, right = _feature_pair(left, right, "fast_dif_fms")
     B, C, H, W = left.shape
     ds, D, per_pixel = _fast_samples(left, disp_sample)
     shape = (B, D, H, W) if normalize else (B, C, D, H, W)
     out = torch.empty(shape, dtype=torch.float32, device=left.device)
-    check(lib.dmb_fast_dif_fms_f32(dev_ptr(left), dev_ptr(right), dev_ptr(ds), dev_ptr(out), B, C, D, H, W, per_pixel,
-                                   1 if normalize else 0, float(p), stream_ptr(left.device)), "dmb_fast_dif_fms_f32")
+    launch("dmb_fast_dif_fms_f32", left, right, ds, out, B, C, D, H, W, per_pixel, 1 if normalize else 0, p)
     return out
 
 
@@ -173,7 +165,6 @@ def fast_fms_bwd(left, right, disp_sample, dvol, dif=False, norm_out=None, p=1.0
     """Backward of fast_cat_fms / fast_dif_fms: (d left, d right, d disp_sample); the first two [B, C, H, W], the third
     [B, D, H, W] with ``wrt_samples`` (per-pixel samples only) and None otherwise.  ``norm_out`` = the forward's output of
     fast_dif_fms(normalize=True, p) selects the normalised form (grad_output [B, D, H, W])."""
-    lib = _lib.load()
     left, right = _feature_pair(left, right, "fast_fms_bwd")
     ds, D, per_pixel = _fast_samples(left, disp_sample)
     dvol = _f32c(dvol, "grad_output")
@@ -191,43 +182,33 @@ def fast_fms_bwd(left, right, disp_sample, dvol, dif=False, norm_out=None, p=1.0
     dl, dr = torch.empty_like(left), torch.empty_like(right)
     dsamp = torch.empty((B, D, H, W), dtype=torch.float32, device=left.device) if wrt_samples else None
     part = torch.empty((B, C, H, 2, W), dtype=torch.float32, device=left.device)
-    check(lib.dmb_fast_fms_bwd_f32(dev_ptr(left), dev_ptr(right), dev_ptr(ds), dev_ptr(dvol), dev_ptr(norm_out, "norm_out", True), dev_ptr(dl),
-                                   dev_ptr(dr), dev_ptr(dsamp, "d_samples", True), dev_ptr(part), B, C, D, H, W, per_pixel, mode, float(p),
-                                   stream_ptr(left.device)), "dmb_fast_fms_bwd_f32")
+    launch("dmb_fast_fms_bwd_f32", left, right, ds, dvol, opt(norm_out), dl, dr, opt(dsamp), part, B, C, D, H, W, per_pixel, mode, p)
     return dl, dr, dsamp
 
 
 def gwc_fms(left, right, disp_idx, num_groups, out=None, out_ch_offset=0):
-    lib = _lib.load()
     left, right = _feature_pair(left, right, "gwc_fms")
     B, C, H, W = left.shape
     D = len(disp_idx)
     if out is None:
         out = torch.empty((B, num_groups, D, H, W), dtype=torch.float32, device=left.device)
-    check(lib.dmb_gwc_fms_f32(dev_ptr(left), dev_ptr(right), dev_ptr(out), B, C, num_groups, H, W, D,
-                              host_ints(disp_idx), out.shape[1], out_ch_offset, stream_ptr(left.device)),
-          "dmb_gwc_fms_f32")
+    launch("dmb_gwc_fms_f32", left, right, out, B, C, num_groups, H, W, D, disp_idx, out.shape[1], out_ch_offset)
     return out
 
 
 def correlation1d(left, right, max_disp, negative_slope=0.1):
     """correlation1d_cost.py:7-27: [B, C, H, W] x 2 -> [B, max_disp, H, W], channel j = disparity max_disp - 1 - j."""
-    lib = _lib.load()
     left, right = _feature_pair(left, right, "correlation1d")
     B, C, H, W = left.shape
     out = torch.empty((B, max_disp, H, W), dtype=torch.float32, device=left.device)
-    check(lib.dmb_correlation1d_f32(dev_ptr(left), dev_ptr(right), dev_ptr(out), B, C, H, W, max_disp, negative_slope,
-                                    stream_ptr(left.device)), "dmb_correlation1d_f32")
+    launch("dmb_correlation1d_f32", left, right, out, B, C, H, W, max_disp, negative_slope)
     return out
 
 
 def cat_fms_into(left, right, disp_idx, out, out_ch_offset):
-    lib = _lib.load()
     left, right = _feature_pair(left, right, "cat_fms_into")
     B, C, H, W = left.shape
-    check(lib.dmb_cat_fms_into_f32(dev_ptr(left), dev_ptr(right), dev_ptr(out), B, C, H, W, len(disp_idx),
-                                   host_ints(disp_idx), out.shape[1], out_ch_offset, stream_ptr(left.device)),
-          "dmb_cat_fms_into_f32")
+    launch("dmb_cat_fms_into_f32", left, right, out, B, C, H, W, len(disp_idx), disp_idx, out.shape[1], out_ch_offset)
     return out
 
 
@@ -238,8 +219,7 @@ def pack_conv3d_weights(w):
     w = _f32c(w, "weight")
     Co, Ci = w.shape[0], w.shape[1]
     wp = torch.empty((lib.dmb_conv3d_packed_floats(Co, Ci),), dtype=torch.float32, device=w.device)
-    check(lib.dmb_conv3d_pack_weights_f32(dev_ptr(w), dev_ptr(wp), Co, Ci, stream_ptr(w.device)),
-          "dmb_conv3d_pack_weights_f32")
+    launch("dmb_conv3d_pack_weights_f32", w, wp, Co, Ci)
     return wp
 
 
@@ -249,8 +229,7 @@ def pack_deconv3d_weights(w):
     w = _f32c(w, "weight")
     Ci, Co = w.shape[0], w.shape[1]
     wp = torch.empty((lib.dmb_deconv3d_packed_floats(Ci, Co),), dtype=torch.float32, device=w.device)
-    check(lib.dmb_deconv3d_pack_weights_f32(dev_ptr(w), dev_ptr(wp), Ci, Co, stream_ptr(w.device)),
-          "dmb_deconv3d_pack_weights_f32")
+    launch("dmb_deconv3d_pack_weights_f32", w, wp, Ci, Co)
     return wp
 
 
@@ -327,6 +306,8 @@ def _unit_conv3d(fn, tag, what, x, wpack, scale, shift, residual, out, out_shape
     timer = _kernel_timer if tag is not None else None
     if timer is not None:
         timer.start(tag)
+    # written out, not ``launch``: the generic call costs 0.6 us of host time per launch, more than the 0.2 .. 0.3 us by which the
+    # ctypes-only unit calls may move (profiles/binding_refactor_bench.log, "marshal_us")
     check(fn(dev_ptr(x), dev_ptr(wpack), dev_ptr(scale, allow_none=True), dev_ptr(shift, allow_none=True),
              dev_ptr(residual, allow_none=True), dev_ptr(y), *dims, *tail, stream_ptr(x.device)), fn.__name__)
     if timer is not None:
@@ -505,22 +486,19 @@ def copy_window(src, Wd, xs):
     sh = _lib.shim()
     if sh is not None:
         return sh.copy_window(src if src.is_contiguous() else src.contiguous(), int(Wd), int(xs))
-    lib = _lib.load()
     src = _f32c(src, "src")
     W = src.shape[-1]
     dst = torch.empty(tuple(src.shape[:-1]) + (Wd,), dtype=torch.float32, device=src.device)
-    rows = src.numel() // W
-    check(lib.dmb_copy_window_f32(dev_ptr(src), dev_ptr(dst), rows, W, Wd, xs, stream_ptr(src.device)), "dmb_copy_window_f32")
+    launch("dmb_copy_window_f32", src, dst, src.numel() // W, W, Wd, xs)
     return dst
 
 
 def zero_columns_(t, x0):
     """t[..., x0:] = 0 in place: the padding columns of a row-padded tensor (see deconv3d_k3s2, ``out_width``)."""
-    lib = _lib.load()
     if t.dtype != torch.float32 or not t.is_contiguous():
         raise _lib.DmbLibraryError("zero_columns_: contiguous float32 tensor expected")
     pitch = t.shape[-1]
-    check(lib.dmb_zero_columns_f32(dev_ptr(t), t.numel() // pitch, pitch, int(x0), stream_ptr(t.device)), "dmb_zero_columns_f32")
+    launch("dmb_zero_columns_f32", t, t.numel() // pitch, pitch, x0)
     return t
 
 
@@ -590,8 +568,7 @@ def catconv_pack(w, kind="cat"):
     C = w.shape[1] if kind == "dif" else w.shape[1] // 2
     n = lib.dmb_conv2d_packed_floats(CATCONV_CH, C, 3)
     buf = torch.empty((5, n), dtype=torch.float32, device=w.device)
-    check(lib.dmb_catconv_pack_weights_f32(dev_ptr(w), dev_ptr(buf), Co, C, CATCONV_CH, 1 if kind == "dif" else 0, stream_ptr(w.device)),
-          "dmb_catconv_pack_weights_f32")
+    launch("dmb_catconv_pack_weights_f32", w, buf, Co, C, CATCONV_CH, 1 if kind == "dif" else 0)
     return {"A": buf[0], "B1": buf[1], "B2": buf[2], "HC": buf[3], "HD": buf[4], "Co": Co, "Cin": C}
 
 
@@ -620,7 +597,6 @@ def catconv_pack_torch(w, kind="cat"):
 def catconv_first(L, R, D, packs, scale=None, shift=None, relu=False):
     """relu?(scale * conv3d(V, w) + shift) without the volume V = cat_fms(L, R, d_k = k) (or dif_fms: the packs decide):
     [B, C, H, W] x 2 -> [B, Co, D, H, W]."""
-    lib = _lib.load()
     L, R = _feature_pair(L, R, "catconv_first")
     B, C, H, W = L.shape
     if packs.get("Cin") is not None and packs["Cin"] != C:
@@ -670,13 +646,9 @@ def catconv_first(L, R, D, packs, scale=None, shift=None, relu=False):
     GM = torch.empty((B, Co, H, W + 4), dtype=torch.float32, device=dev)
     GB = torch.empty((B, Co, H, D), dtype=torch.float32, device=dev)
     # (FB holds m = 1 in channels [0, CA) and m = 2 in [CA, 2 CA), each as dz * Co + co like FA)
-    check(lib.dmb_catconv_finalize_f32(dev_ptr(FA), dev_ptr(FB), dev_ptr(HC), dev_ptr(HD), dev_ptr(FM), dev_ptr(BAND),
-                                       dev_ptr(GM), dev_ptr(GB), B, Co, CA, 2 * CA, D, H, W, Wc, stream_ptr(dev)),
-          "dmb_catconv_finalize_f32")
+    launch("dmb_catconv_finalize_f32", FA, FB, HC, HD, FM, BAND, GM, GB, B, Co, CA, 2 * CA, D, H, W, Wc)
     out = torch.empty((B, Co, D, H, W), dtype=torch.float32, device=dev)
-    check(lib.dmb_catconv_combine_f32(dev_ptr(FA), dev_ptr(HC), dev_ptr(FM), dev_ptr(BAND), dev_ptr(GM), dev_ptr(GB),
-                                      dev_ptr(scale, allow_none=True), dev_ptr(shift, allow_none=True), dev_ptr(out), B, Co, CA,
-                                      D, H, W, _relu_mode(relu), stream_ptr(dev)), "dmb_catconv_combine_f32")
+    launch("dmb_catconv_combine_f32", FA, HC, FM, BAND, GM, GB, opt(scale), opt(shift), out, B, Co, CA, D, H, W, _relu_mode(relu))
     return out
 
 
@@ -708,8 +680,7 @@ def pack_conv3d_x6_weights(w):
     w = _f32c(w, "weight")
     Co, Ci = w.shape[0], w.shape[1]
     wp = torch.empty((lib.dmb_conv3d_x6_packed_bytes(Co, Ci) // 4,), dtype=torch.float32, device=w.device)
-    check(lib.dmb_conv3d_x6_pack_weights_f32(dev_ptr(w), dev_ptr(wp), Co, Ci, stream_ptr(w.device)),
-          "dmb_conv3d_x6_pack_weights_f32")
+    launch("dmb_conv3d_x6_pack_weights_f32", w, wp, Co, Ci)
     return wp
 
 
@@ -725,7 +696,6 @@ def conv3d_k3_c1(x, w, bias=0.0, residual=None):
     if sh is not None:
         return sh.conv3d_k3_c1(x if x.is_contiguous() else x.contiguous(), w if w.is_contiguous() else w.contiguous(), float(bias),
                                residual, _conv_flags())
-    lib = _lib.load()
     x, w = _f32c(x, "x"), _f32c(w, "weight")
     B, Ci, D, H, W = x.shape
     y = torch.empty((B, 1, D, H, W), dtype=torch.float32, device=x.device)
@@ -733,8 +703,7 @@ def conv3d_k3_c1(x, w, bias=0.0, residual=None):
         raise _lib.DmbLibraryError("conv3d_k3_c1: weight %s for %d input channels" % (tuple(w.shape), Ci))
     if residual is not None:
         _same_shape(residual, y, "conv3d_k3_c1 residual")
-    check(lib.dmb_conv3d_k3_c1_f32(dev_ptr(x), dev_ptr(w), float(bias), dev_ptr(residual, allow_none=True), dev_ptr(y),
-                                   B, Ci, D, H, W, _conv_flags(), stream_ptr(x.device)), "dmb_conv3d_k3_c1_f32")
+    launch("dmb_conv3d_k3_c1_f32", x, w, bias, opt(residual), y, B, Ci, D, H, W, _conv_flags())
     return y
 
 
@@ -804,8 +773,7 @@ def pack_conv3d_dgrad_weights(w):
     w = _f32c(w, "weight")
     Co, Ci = w.shape[0], w.shape[1]
     wp = torch.empty((lib.dmb_conv3d_packed_floats(Ci, Co),), dtype=torch.float32, device=w.device)
-    check(lib.dmb_conv3d_pack_dgrad_weights_f32(dev_ptr(w), dev_ptr(wp), Co, Ci, stream_ptr(w.device)),
-          "dmb_conv3d_pack_dgrad_weights_f32")
+    launch("dmb_conv3d_pack_dgrad_weights_f32", w, wp, Co, Ci)
     return wp
 
 
@@ -850,9 +818,7 @@ def make_pack_table(jobs, device):
 
 
 def run_pack_table(table, njobs):
-    lib = _lib.load()
-    check(lib.dmb_conv3d_pack_weights_multi_f32(ctypes.c_void_p(table.data_ptr()), int(njobs), stream_ptr(table.device)),
-          "dmb_conv3d_pack_weights_multi_f32")
+    launch("dmb_conv3d_pack_weights_multi_f32", ctypes.c_void_p(table.data_ptr()), njobs, device=table.device)
 
 
 def conv3d_k3_dgrad(dc, w, stride=1, in_size=None, residual=None, wpack=None):
@@ -931,8 +897,7 @@ def conv3d_k3_wgrad(x, dc):
         raise _lib.DmbLibraryError("conv3d_k3_wgrad: dc shape %s does not match x %s" % (tuple(dc.shape), tuple(x.shape)))
     dw = torch.empty((Co, Ci, 3, 3, 3), dtype=torch.float32, device=x.device)
     ws = torch.empty((lib.dmb_conv3d_wgrad_workspace_floats(Co, Ci),), dtype=torch.float32, device=x.device)
-    check(lib.dmb_conv3d_k3_wgrad_f32(dev_ptr(x), dev_ptr(dc), dev_ptr(dw), dev_ptr(ws), B, Ci, Co, D, H, W,
-                                      stream_ptr(x.device)), "dmb_conv3d_k3_wgrad_f32")
+    launch("dmb_conv3d_k3_wgrad_f32", x, dc, dw, ws, B, Ci, Co, D, H, W)
     return dw
 
 
@@ -945,8 +910,7 @@ def _s2_wgrad(small, big, what):
         raise _lib.DmbLibraryError("%s: batch sizes differ" % what)
     dw = torch.empty((Cs, Cb, 3, 3, 3), dtype=torch.float32, device=small.device)
     ws = torch.empty((lib.dmb_conv3d_wgrad_workspace_floats(Cs, Cb),), dtype=torch.float32, device=small.device)
-    check(lib.dmb_conv3d_k3s2_wgrad_f32(dev_ptr(small), dev_ptr(big), dev_ptr(dw), dev_ptr(ws), B, Cs, Cb, Ds, Hs, Ws, Db, Hb, Wb,
-                                        stream_ptr(small.device)), what)
+    launch("dmb_conv3d_k3s2_wgrad_f32", small, big, dw, ws, B, Cs, Cb, Ds, Hs, Ws, Db, Hb, Wb)
     return dw
 
 
@@ -979,8 +943,7 @@ def conv2d_wgrad(x, dc, ksize=3, dilation=1):
         return sh.conv2d_wgrad(x, dc, int(ksize), int(dilation))
     dw = torch.empty((Co, Ci, ksize, ksize), dtype=torch.float32, device=x.device)
     ws = torch.empty((lib.dmb_conv2d_wgrad_workspace_floats(Co, Ci),), dtype=torch.float32, device=x.device)
-    check(lib.dmb_conv2d_wgrad_f32(dev_ptr(x), dev_ptr(dc), dev_ptr(dw), dev_ptr(ws), B, Ci, Co, H, W, int(ksize), int(dilation),
-                                   stream_ptr(x.device)), "dmb_conv2d_wgrad_f32")
+    launch("dmb_conv2d_wgrad_f32", x, dc, dw, ws, B, Ci, Co, H, W, ksize, dilation)
     return dw
 
 
@@ -1038,10 +1001,7 @@ def bn_train_stats(c, gamma=None, beta=None, running_mean=None, running_var=None
     B, C, S = _bcs(c)
     out = [torch.empty((C,), dtype=torch.float32, device=c.device) for _ in range(4)]
     ws = torch.empty((lib.dmb_bn_workspace_doubles(C, S),), dtype=torch.float64, device=c.device)
-    check(lib.dmb_bn_train_stats_f32(dev_ptr(c), dev_ptr(gamma, allow_none=True), dev_ptr(beta, allow_none=True),
-                                     dev_ptr(running_mean, allow_none=True), dev_ptr(running_var, allow_none=True),
-                                     float(momentum), float(eps), dev_ptr(out[0]), dev_ptr(out[1]), dev_ptr(out[2]),
-                                     dev_ptr(out[3]), dev_ptr(ws), B, C, S, stream_ptr(c.device)), "dmb_bn_train_stats_f32")
+    launch("dmb_bn_train_stats_f32", c, opt(gamma), opt(beta), opt(running_mean), opt(running_var), momentum, eps, *out, ws, B, C, S)
     return tuple(out)
 
 
@@ -1058,8 +1018,7 @@ def conv3d_k3_bnstats(x, wpack, Co):
     _pack_ok(wpack, lib.dmb_conv3d_packed_floats(Co, Ci), Ci, Co, "conv3d_k3_bnstats")
     raw = torch.empty((B, Co, D, H, W), dtype=torch.float32, device=x.device)
     parts = torch.empty((Co, P, 2), dtype=torch.float64, device=x.device)
-    check(lib.dmb_conv3d_k3_bnstats_f32(dev_ptr(x), dev_ptr(wpack), dev_ptr(raw), dev_ptr(parts), B, Ci, Co, D, H, W, stream_ptr(x.device)),
-          "dmb_conv3d_k3_bnstats_f32")
+    launch("dmb_conv3d_k3_bnstats_f32", x, wpack, raw, parts, B, Ci, Co, D, H, W)
     return raw, parts
 
 
@@ -1067,7 +1026,6 @@ def bn_train_act(c, partials, gamma=None, beta=None, running_mean=None, running_
                  residual=None, relu=False):
     """bn_train_fwd without its pass over ``c`` for the block sums: the statistics are finished from ``partials`` ([C, P, 2] float64
     sums of c and c^2, conv3d_k3_bnstats).  Returns (y, mean, invstd, scale, shift)."""
-    lib = _lib.load()
     c = _f32c(c, "c")
     B, C, S = _bcs(c)
     if partials.dtype != torch.float64 or partials.dim() != 3 or partials.shape[0] != C or partials.shape[2] != 2 or not partials.is_contiguous():
@@ -1078,12 +1036,8 @@ def bn_train_act(c, partials, gamma=None, beta=None, running_mean=None, running_
         raise _lib.DmbLibraryError("bn_train_act: num_batches_tracked must be an int64 tensor on %s" % c.device)
     y = torch.empty_like(c)
     stats = torch.empty((4, C), dtype=torch.float32, device=c.device)
-    check(lib.dmb_bn_train_act_f32(dev_ptr(c), dev_ptr(partials), int(partials.shape[1]), dev_ptr(gamma, allow_none=True),
-                                   dev_ptr(beta, allow_none=True), dev_ptr(running_mean, allow_none=True),
-                                   dev_ptr(running_var, allow_none=True), dev_ptr(num_batches_tracked, allow_none=True),
-                                   float(momentum), float(eps), dev_ptr(stats[0]), dev_ptr(stats[1]), dev_ptr(stats[2]), dev_ptr(stats[3]),
-                                   dev_ptr(residual, allow_none=True), dev_ptr(y), B, C, S, _relu_mode(relu), stream_ptr(c.device)),
-          "dmb_bn_train_act_f32")
+    launch("dmb_bn_train_act_f32", c, partials, partials.shape[1], opt(gamma), opt(beta), opt(running_mean), opt(running_var),
+           opt(num_batches_tracked), momentum, eps, stats[0], stats[1], stats[2], stats[3], opt(residual), y, B, C, S, _relu_mode(relu))
     written = [t for t in (running_mean, running_var, num_batches_tracked) if t is not None]
     if written:
         torch.autograd.graph.increment_version(written)
@@ -1092,12 +1046,10 @@ def bn_train_act(c, partials, gamma=None, beta=None, running_mean=None, running_
 
 def bn_act(c, scale, shift, residual=None, relu=False):
     """y = act(c*scale + shift (+ residual)); relu as in conv3d_k3 (False / True / 'pre')."""
-    lib = _lib.load()
     c = _f32c(c, "c")
     B, C, S = _bcs(c)
     y = torch.empty_like(c)
-    check(lib.dmb_bn_act_f32(dev_ptr(c), dev_ptr(scale), dev_ptr(shift), dev_ptr(residual, allow_none=True), dev_ptr(y),
-                             B, C, S, _relu_mode(relu), stream_ptr(c.device)), "dmb_bn_act_f32")
+    launch("dmb_bn_act_f32", c, scale, shift, opt(residual), y, B, C, S, _relu_mode(relu))
     return y
 
 
@@ -1120,12 +1072,8 @@ def bn_train_fwd(c, gamma=None, beta=None, running_mean=None, running_var=None, 
         raise _lib.DmbLibraryError("bn_train_fwd: num_batches_tracked must be an int64 tensor on %s" % c.device)
     stats = torch.empty((4, C), dtype=torch.float32, device=c.device)
     ws = torch.empty((lib.dmb_bn_workspace_doubles(C, S),), dtype=torch.float64, device=c.device)
-    check(lib.dmb_bn_train_fwd_f32(dev_ptr(c), dev_ptr(gamma, allow_none=True), dev_ptr(beta, allow_none=True),
-                                   dev_ptr(running_mean, allow_none=True), dev_ptr(running_var, allow_none=True),
-                                   None if num_batches_tracked is None else ctypes.c_void_p(num_batches_tracked.data_ptr()),
-                                   float(momentum), float(eps), dev_ptr(stats[0]), dev_ptr(stats[1]), dev_ptr(stats[2]),
-                                   dev_ptr(stats[3]), dev_ptr(residual, allow_none=True), dev_ptr(y), dev_ptr(ws), B, C, S,
-                                   _relu_mode(relu), stream_ptr(c.device)), "dmb_bn_train_fwd_f32")
+    launch("dmb_bn_train_fwd_f32", c, opt(gamma), opt(beta), opt(running_mean), opt(running_var), opt(num_batches_tracked), momentum,
+           eps, stats[0], stats[1], stats[2], stats[3], opt(residual), y, ws, B, C, S, _relu_mode(relu))
     # the kernel wrote these through their pointers: tell torch (the modules' folded-parameter caches key on the versions --
     # rounds 1-5 relied on the ``num_batches_tracked += 1`` launch for that)
     written = [t for t in (running_mean, running_var, num_batches_tracked) if t is not None]
@@ -1156,10 +1104,8 @@ def bn_act_bwd(dy, c, y, scale, shift, mean, invstd, relu=False, training=True, 
     dres = torch.empty_like(c) if want_dres else None
     gb = torch.empty((2, C), dtype=torch.float32, device=c.device)
     ws = torch.empty((lib.dmb_bn_workspace_doubles(C, S),), dtype=torch.float64, device=c.device)
-    check(lib.dmb_bn_act_bwd_f32(dev_ptr(dy), dev_ptr(c), dev_ptr(y, allow_none=mode != 1), dev_ptr(scale), dev_ptr(shift),
-                                 dev_ptr(mean), dev_ptr(invstd), dev_ptr(ws), dev_ptr(gb[0]), dev_ptr(gb[1]), dev_ptr(dc),
-                                 dev_ptr(dres, allow_none=True), dev_ptr(dres_acc, allow_none=True), B, C, S, mode,
-                                 1 if training else 0, stream_ptr(c.device)), "dmb_bn_act_bwd_f32")
+    launch("dmb_bn_act_bwd_f32", dy, c, y if mode == 1 else opt(y), scale, shift, mean, invstd, ws, gb[0], gb[1], dc, opt(dres),
+           opt(dres_acc), B, C, S, mode, 1 if training else 0)
     return dc, gb[0], gb[1], dres
 
 
@@ -1172,36 +1118,32 @@ def channel_dot(a, g):
         raise _lib.DmbLibraryError("channel_dot: g shape %s does not match a %s" % (tuple(g.shape), tuple(a.shape)))
     out = torch.empty((C,), dtype=torch.float32, device=a.device)
     ws = torch.empty((lib.dmb_bn_workspace_doubles(C, S),), dtype=torch.float64, device=a.device)
-    check(lib.dmb_channel_dot_f32(dev_ptr(a), dev_ptr(g), dev_ptr(ws), dev_ptr(out), B, C, S, stream_ptr(a.device)), "dmb_channel_dot_f32")
+    launch("dmb_channel_dot_f32", a, g, ws, out, B, C, S)
     return out
 
 
 # ---------------------------------------------------------------------------------------------- path ends, backward
 def _volume_bwd(fn_name, dvol, disp_idx, C):
-    lib = _lib.load()
     dvol = _f32c(dvol, "dvol")
     B, VC, D, H, W = dvol.shape
     if D != len(disp_idx) or VC != (2 * C if fn_name == "dmb_cat_fms_bwd_f32" else C):
         raise _lib.DmbLibraryError("%s: gradient shape %s does not match C=%d, D=%d" % (fn_name, tuple(dvol.shape), C, len(disp_idx)))
     dL = torch.empty((B, C, H, W), dtype=torch.float32, device=dvol.device)
     dR = torch.empty_like(dL)
-    check(getattr(lib, fn_name)(dev_ptr(dvol), dev_ptr(dL), dev_ptr(dR), B, C, H, W, D, host_ints(disp_idx),
-                                stream_ptr(dvol.device)), fn_name)
+    launch(fn_name, dvol, dL, dR, B, C, H, W, D, disp_idx)
     return dL, dR
 
 
 def cat_first_wgrad(left, right, dc, kind="cat"):
     """Weight gradient [Co, 2C (cat) | C (dif), 3, 3, 3] of the first convolution on the volume of cat_fms / dif_fms(left, right) with
     unit disparity step, from dc [B, Co, D, H, W], without the volume: dmb_cat_first_wgrad_maps_f32 + two 2-D weight gradients."""
-    lib = _lib.load()
     left, right, dc = _f32c(left, "left"), _f32c(right, "right"), _f32c(dc, "dc")
     B, Co, D, H, W = dc.shape
     C = left.shape[1]
     if tuple(left.shape) != (B, C, H, W) or tuple(right.shape) != (B, C, H, W):
         raise _lib.DmbLibraryError("cat_first_wgrad: feature maps %s / %s do not belong to dc %s" % (tuple(left.shape), tuple(right.shape), tuple(dc.shape)))
     maps = torch.empty((2, B, 9 * Co, H, W), dtype=torch.float32, device=dc.device)
-    check(lib.dmb_cat_first_wgrad_maps_f32(dev_ptr(dc), dev_ptr(maps[0]), dev_ptr(maps[1]), B, Co, D, H, W, stream_ptr(dc.device)),
-          "dmb_cat_first_wgrad_maps_f32")
+    launch("dmb_cat_first_wgrad_maps_f32", dc, maps[0], maps[1], B, Co, D, H, W)
     dl = conv2d_wgrad(left, maps[0], 3, 1).view(3, 3, Co, C, 3, 3)     # [dz, dx, co, ci, dy', dx']
     dr = conv2d_wgrad(right, maps[1], 3, 1).view(3, 3, Co, C, 3, 3)
     wl = torch.diagonal(dl, dim1=1, dim2=5).permute(1, 2, 0, 3, 4)      # tap dx' = dx  -> [co, ci, dz, dy, dx]
@@ -1219,19 +1161,16 @@ def dif_fms_bwd(dvol, disp_idx):
 
 
 def soft_argmin_bwd(cost, disp, grad_disp, disp_values, alpha=1.0):
-    lib = _lib.load()
     cost, disp, grad_disp = _f32c(cost, "cost"), _f32c(disp, "disp"), _f32c(grad_disp, "grad_disp")
     B, D, H, W = cost.shape
     out = torch.empty_like(cost)
-    check(lib.dmb_soft_argmin_bwd_f32(dev_ptr(cost), dev_ptr(disp), dev_ptr(grad_disp), dev_ptr(out), B, D, H, W,
-                                      float(alpha), host_floats(disp_values), stream_ptr(cost.device)), "dmb_soft_argmin_bwd_f32")
+    launch("dmb_soft_argmin_bwd_f32", cost, disp, grad_disp, out, B, D, H, W, alpha, disp_values)
     return out
 
 
 def trilinear_ac_soft_argmin_bwd(x, disp, grad_disp, out_size, disp_values, alpha=1.0, grad_cost=None):
     """Gradient of trilinear_ac_soft_argmin w.r.t. the low-resolution cost x [B, Di, Hi, Wi]: through the disparity
     (grad_disp) and, if given, through the up-sampled volume itself (grad_cost [B, Do, Ho, Wo])."""
-    lib = _lib.load()
     x, disp, grad_disp = _f32c(x, "x"), _f32c(disp, "disp"), _f32c(grad_disp, "grad_disp")
     B, Di, Hi, Wi = x.shape
     Do, Ho, Wo = out_size
@@ -1241,53 +1180,46 @@ def trilinear_ac_soft_argmin_bwd(x, disp, grad_disp, out_size, disp_values, alph
             raise _lib.DmbLibraryError("trilinear_ac_soft_argmin_bwd: grad_cost shape %s" % (tuple(grad_cost.shape),))
     scratch = torch.empty((B, Di, Ho, Wo), dtype=torch.float32, device=x.device)
     gx = torch.empty_like(x)
-    check(lib.dmb_trilinear_ac_soft_argmin_bwd_f32(dev_ptr(x), dev_ptr(disp), dev_ptr(grad_disp), dev_ptr(grad_cost, allow_none=True),
-                                                   dev_ptr(scratch), dev_ptr(gx), B, Di, Hi, Wi, Do, Ho, Wo, float(alpha),
-                                                   host_floats(disp_values), stream_ptr(x.device)), "dmb_trilinear_ac_soft_argmin_bwd_f32")
+    launch("dmb_trilinear_ac_soft_argmin_bwd_f32", x, disp, grad_disp, opt(grad_cost), scratch, gx, B, Di, Hi, Wi, Do, Ho, Wo, alpha,
+           disp_values)
     return gx
 
 
 def trilinear_ac_bwd(grad_y, in_size):
     """Gradient of trilinear_ac w.r.t. its input: grad_y [B, Do, Ho, Wo] -> [B, Di, Hi, Wi]."""
-    lib = _lib.load()
     grad_y = _f32c(grad_y, "grad_y")
     B, Do, Ho, Wo = grad_y.shape
     Di, Hi, Wi = in_size
     scratch = torch.empty((B, Di, Ho, Wo), dtype=torch.float32, device=grad_y.device)
     gx = torch.empty((B, Di, Hi, Wi), dtype=torch.float32, device=grad_y.device)
-    check(lib.dmb_trilinear_ac_bwd_f32(dev_ptr(grad_y), dev_ptr(scratch), dev_ptr(gx), B, Di, Hi, Wi, Do, Ho, Wo,
-                                       stream_ptr(grad_y.device)), "dmb_trilinear_ac_bwd_f32")
+    launch("dmb_trilinear_ac_bwd_f32", grad_y, scratch, gx, B, Di, Hi, Wi, Do, Ho, Wo)
     return gx
 
 
 def avgpool2d_bwd(grad_y, in_hw, k):
-    lib = _lib.load()
     grad_y = _f32c(grad_y, "grad_y")
     B, C = grad_y.shape[0], grad_y.shape[1]
     H, W = in_hw
     gx = torch.empty((B, C, H, W), dtype=torch.float32, device=grad_y.device)
-    check(lib.dmb_avgpool2d_bwd_f32(dev_ptr(grad_y), dev_ptr(gx), B, C, H, W, int(k), stream_ptr(grad_y.device)), "dmb_avgpool2d_bwd_f32")
+    launch("dmb_avgpool2d_bwd_f32", grad_y, gx, B, C, H, W, k)
     return gx
 
 
 def bilinear_ac_bwd(grad_y, in_hw):
-    lib = _lib.load()
     grad_y = _f32c(grad_y, "grad_y")
     B, C, Ho, Wo = grad_y.shape
     Hi, Wi = in_hw
     gx = torch.empty((B, C, Hi, Wi), dtype=torch.float32, device=grad_y.device)
-    check(lib.dmb_bilinear_ac_bwd_f32(dev_ptr(grad_y), dev_ptr(gx), B, C, Hi, Wi, Ho, Wo, stream_ptr(grad_y.device)), "dmb_bilinear_ac_bwd_f32")
+    launch("dmb_bilinear_ac_bwd_f32", grad_y, gx, B, C, Hi, Wi, Ho, Wo)
     return gx
 
 
 def bilinear_scale_bwd(grad_y, in_hw, mult):
-    lib = _lib.load()
     grad_y = _f32c(grad_y, "grad_y")
     B, C, Ho, Wo = grad_y.shape
     Hi, Wi = in_hw
     gx = torch.empty((B, C, Hi, Wi), dtype=torch.float32, device=grad_y.device)
-    check(lib.dmb_bilinear_scale_bwd_f32(dev_ptr(grad_y), dev_ptr(gx), B, C, Hi, Wi, Ho, Wo, float(mult), stream_ptr(grad_y.device)),
-          "dmb_bilinear_scale_bwd_f32")
+    launch("dmb_bilinear_scale_bwd_f32", grad_y, gx, B, C, Hi, Wi, Ho, Wo, mult)
     return gx
 
 
@@ -1301,81 +1233,65 @@ def deconv3d_k8s4_c1_bwd(x, w, dy, want_dx=True, want_dw=True):
     dx = torch.empty_like(x) if want_dx else None
     dw = torch.empty((8, 8, 8), dtype=torch.float32, device=x.device) if want_dw else None
     ws = torch.empty((lib.dmb_deconv3d_k8s4_bwd_workspace_doubles(),), dtype=torch.float64, device=x.device) if want_dw else None
-    check(lib.dmb_deconv3d_k8s4_c1_bwd_f32(dev_ptr(x), dev_ptr(w), dev_ptr(dy), dev_ptr(dx, allow_none=True),
-                                           dev_ptr(dw, allow_none=True), dev_ptr(ws, allow_none=True), B, D, H, W,
-                                           stream_ptr(x.device)), "dmb_deconv3d_k8s4_c1_bwd_f32")
+    launch("dmb_deconv3d_k8s4_c1_bwd_f32", x, w, dy, opt(dx), opt(dw), opt(ws), B, D, H, W)
     return dx, dw
 
 
 # ---------------------------------------------------------------------------------------------- upsampling
 def trilinear_ac(x, out_size):
     """x: [B, Di, Hi, Wi] (single channel squeezed) -> [B, Do, Ho, Wo], align_corners=True."""
-    lib = _lib.load()
     x = _f32c(x, "x")
     B, Di, Hi, Wi = x.shape
     Do, Ho, Wo = out_size
     y = torch.empty((B, Do, Ho, Wo), dtype=torch.float32, device=x.device)
-    check(lib.dmb_trilinear_ac_f32(dev_ptr(x), dev_ptr(y), B, Di, Hi, Wi, Do, Ho, Wo, stream_ptr(x.device)),
-          "dmb_trilinear_ac_f32")
+    launch("dmb_trilinear_ac_f32", x, y, B, Di, Hi, Wi, Do, Ho, Wo)
     return y
 
 
 def deconv3d_k8s4_c1(x, w):
     """x: [B, D, H, W], w: [8, 8, 8] (ConvTranspose3d(1,1,8,4,2) weight squeezed) -> [B, 4D, 4H, 4W]."""
-    lib = _lib.load()
     x, w = _f32c(x, "x"), _f32c(w, "weight")
     B, D, H, W = x.shape
     y = torch.empty((B, 4 * D, 4 * H, 4 * W), dtype=torch.float32, device=x.device)
-    check(lib.dmb_deconv3d_k8s4_c1_f32(dev_ptr(x), dev_ptr(w), dev_ptr(y), B, D, H, W, stream_ptr(x.device)),
-          "dmb_deconv3d_k8s4_c1_f32")
+    launch("dmb_deconv3d_k8s4_c1_f32", x, w, y, B, D, H, W)
     return y
 
 
 # ---------------------------------------------------------------------------------------------- regression
 def soft_argmin(cost, disp_values, alpha=1.0, normalize=True):
-    lib = _lib.load()
     cost = _f32c(cost, "cost_volume")
     B, D, H, W = cost.shape
     if len(disp_values) != D:
         raise _lib.DmbLibraryError("The number of disparity samples should be consistent!")
     disp = torch.empty((B, 1, H, W), dtype=torch.float32, device=cost.device)
-    check(lib.dmb_soft_argmin_f32(dev_ptr(cost), dev_ptr(disp), B, D, H, W, float(alpha), int(bool(normalize)),
-                                  host_floats(disp_values), stream_ptr(cost.device)), "dmb_soft_argmin_f32")
+    launch("dmb_soft_argmin_f32", cost, disp, B, D, H, W, alpha, int(bool(normalize)), disp_values)
     return disp
 
 
 def soft_argmin_sampled(cost, disp_sample, alpha=1.0, normalize=True):
-    lib = _lib.load()
     cost, disp_sample = _f32c(cost, "cost_volume"), _f32c(disp_sample, "disp_sample")
     B, D, H, W = cost.shape
     _same_shape(disp_sample, cost, "soft_argmin: cost volume and per-pixel disparity samples")
     disp = torch.empty((B, 1, H, W), dtype=torch.float32, device=cost.device)
-    check(lib.dmb_soft_argmin_sampled_f32(dev_ptr(cost), dev_ptr(disp_sample), dev_ptr(disp), B, D, H, W, float(alpha),
-                                          int(bool(normalize)), stream_ptr(cost.device)), "dmb_soft_argmin_sampled_f32")
+    launch("dmb_soft_argmin_sampled_f32", cost, disp_sample, disp, B, D, H, W, alpha, int(bool(normalize)))
     return disp
 
 
 def local_soft_argmin(cost, radius, radius_dilation=1, start_disp=0, dilation=1, alpha=1.0, return_index=False):
-    lib = _lib.load()
     cost = _f32c(cost, "cost_volume")
     B, D, H, W = cost.shape
     disp = torch.empty((B, 1, H, W), dtype=torch.float32, device=cost.device)
     idx = torch.empty((B, 1, H, W), dtype=torch.int64, device=cost.device) if return_index else None
-    check(lib.dmb_local_soft_argmin_f32(dev_ptr(cost), dev_ptr(disp), dev_ptr(idx, allow_none=True), B, D, H, W,
-                                        int(radius), int(radius_dilation), int(start_disp), int(dilation), float(alpha),
-                                        stream_ptr(cost.device)), "dmb_local_soft_argmin_f32")
+    launch("dmb_local_soft_argmin_f32", cost, disp, opt(idx), B, D, H, W, radius, radius_dilation, start_disp, dilation, alpha)
     return (disp, idx) if return_index else disp
 
 
 def trilinear_soft_argmin(x, out_size, disp_values, alpha=1.0):
-    lib = _lib.load()
     x = _f32c(x, "x")
     B, Di, Hi, Wi = x.shape
     Do, Ho, Wo = out_size
     disp = torch.empty((B, 1, Ho, Wo), dtype=torch.float32, device=x.device)
-    check(lib.dmb_trilinear_soft_argmin_f32(dev_ptr(x), dev_ptr(disp), B, Di, Hi, Wi, Do, Ho, Wo, float(alpha),
-                                            host_floats(disp_values), stream_ptr(x.device)),
-          "dmb_trilinear_soft_argmin_f32")
+    launch("dmb_trilinear_soft_argmin_f32", x, disp, B, Di, Hi, Wi, Do, Ho, Wo, alpha, disp_values)
     return disp
 
 
@@ -1387,22 +1303,18 @@ def trilinear_ac_soft_argmin(x, out_size, disp_values, alpha=1.0):
         y, disp = sh.trilinear_ac_soft_argmin(x if x.is_contiguous() else x.contiguous(), int(out_size[0]), int(out_size[1]), int(out_size[2]),
                                               float(alpha), [float(v) for v in disp_values])
         return y, disp
-    lib = _lib.load()
     x = _f32c(x, "x")
     B, Di, Hi, Wi = x.shape
     Do, Ho, Wo = out_size
     y = torch.empty((B, Do, Ho, Wo), dtype=torch.float32, device=x.device)
     disp = torch.empty((B, 1, Ho, Wo), dtype=torch.float32, device=x.device)
-    check(lib.dmb_trilinear_ac_soft_argmin_f32(dev_ptr(x), dev_ptr(y), dev_ptr(disp), B, Di, Hi, Wi, Do, Ho, Wo,
-                                               float(alpha), host_floats(disp_values), stream_ptr(x.device)),
-          "dmb_trilinear_ac_soft_argmin_f32")
+    launch("dmb_trilinear_ac_soft_argmin_f32", x, y, disp, B, Di, Hi, Wi, Do, Ho, Wo, alpha, disp_values)
     return y, disp
 
 
 def deconv3d_k8s4_c1_soft_argmin(x, w, disp_values=None, alpha=1.0):
     """AcfNet's learned 4x up-sampling (ConvTranspose3d(1, 1, 8, 4, 2)) of x [B, D, H, W] AND, when ``disp_values`` is given,
     the soft-argmin (normalize=True) of the volume it writes, in one pass: returns (cost [B, 4D, 4H, 4W], disp or None)."""
-    lib = _lib.load()
     x, w = _f32c(x, "x"), _f32c(w, "weight")
     if x.dim() != 4:
         raise _lib.DmbLibraryError("deconv3d_k8s4_c1_soft_argmin: x must be [B, D, H, W], got %s" % (tuple(x.shape),))
@@ -1413,9 +1325,7 @@ def deconv3d_k8s4_c1_soft_argmin(x, w, disp_values=None, alpha=1.0):
         raise _lib.DmbLibraryError("deconv3d_k8s4_c1_soft_argmin: %d disparity samples for %d output planes" % (len(disp_values), 4 * D))
     y = torch.empty((B, 4 * D, 4 * H, 4 * W), dtype=torch.float32, device=x.device)
     disp = torch.empty((B, 1, 4 * H, 4 * W), dtype=torch.float32, device=x.device) if disp_values is not None else None
-    check(lib.dmb_deconv3d_k8s4_c1_soft_argmin_f32(dev_ptr(x), dev_ptr(w), dev_ptr(y), dev_ptr(disp, allow_none=True), B, D, H, W,
-                                                   float(alpha), host_floats(disp_values) if disp_values is not None else None,
-                                                   stream_ptr(x.device)), "dmb_deconv3d_k8s4_c1_soft_argmin_f32")
+    launch("dmb_deconv3d_k8s4_c1_soft_argmin_f32", x, w, y, opt(disp), B, D, H, W, alpha, opt(disp_values))
     return y, disp
 
 
@@ -1450,19 +1360,16 @@ def pack_conf_head_weights(w1):
     w1 = _f32c(w1, "weight")
     Cm, D = w1.shape[0], w1.shape[1]
     wp = torch.empty((lib.dmb_conf_head_packed_floats(Cm, D),), dtype=torch.float32, device=w1.device)
-    check(lib.dmb_conf_head_pack_weights_f32(dev_ptr(w1), dev_ptr(wp), Cm, D, stream_ptr(w1.device)),
-          "dmb_conf_head_pack_weights_f32")
+    launch("dmb_conf_head_pack_weights_f32", w1, wp, Cm, D)
     return wp
 
 
 def conf_head(cost, w1pack, scale, shift, w2):
-    lib = _lib.load()
     cost = _f32c(cost, "cost")
     B, D, H, W = cost.shape
     Cm = scale.numel()
     conf = torch.empty((B, 1, H, W), dtype=torch.float32, device=cost.device)
-    check(lib.dmb_conf_head_f32(dev_ptr(cost), dev_ptr(w1pack), dev_ptr(scale), dev_ptr(shift), dev_ptr(w2),
-                                dev_ptr(conf), B, D, Cm, H, W, stream_ptr(cost.device)), "dmb_conf_head_f32")
+    launch("dmb_conf_head_f32", cost, w1pack, scale, shift, w2, conf, B, D, Cm, H, W)
     return conf
 
 
@@ -1548,7 +1455,6 @@ def set_conf_dot_epilogue(flag):
 
 def conf_head_from_source(cost, comp, scale, shift, w2):
     """The confidence map of ``cost`` (which carries an UpsampleSource) through the composed quarter-resolution form."""
-    lib = _lib.load()
     src = UpsampleSource.lookup(cost)
     c = _f32c(src.c, "quarter-resolution cost")
     B, Dq, Hq, Wq = c.shape
@@ -1560,24 +1466,21 @@ def conf_head_from_source(cost, comp, scale, shift, w2):
         w2c = _f32c(w2.reshape(-1), "w2")
         if "pack_all" not in comp:
             comp["pack_all"] = torch.cat([wp.reshape(-1) for wp in comp["packs"]]).contiguous()   # the 8 weight sets back to back
-        check(lib.dmb_conf_phase_conv2d_f32(dev_ptr(c), dev_ptr(comp["pack_all"]), dev_ptr(comp["scale"]), dev_ptr(comp["shift"]),
-                                            dev_ptr(w2c), dev_ptr(conf), B, Dq, Hq, Wq, 8, stream_ptr(c.device)), "dmb_conf_phase_conv2d_f32")
+        launch("dmb_conf_phase_conv2d_f32", c, comp["pack_all"], comp["scale"], comp["shift"], w2c, conf, B, Dq, Hq, Wq, 8)
     else:
         hq = torch.empty((B, 16 * M, Hq, Wq), dtype=torch.float32, device=c.device)
         for i, wp in enumerate(comp["packs"]):
             conv2d(c, wp, 128, 3, scale=comp["scale"], shift=comp["shift"], relu=True, out=hq, out_ch_offset=128 * i)
-        check(lib.dmb_conf_gather_f32(dev_ptr(hq), dev_ptr(w2), dev_ptr(conf), B, M, Hq, Wq, stream_ptr(c.device)), "dmb_conf_gather_f32")
-    check(lib.dmb_conf_ring_f32(dev_ptr(cost), dev_ptr(comp["w1t"]), dev_ptr(scale), dev_ptr(shift), dev_ptr(w2), dev_ptr(conf),
-                                B, 4 * Dq, M, 4 * Hq, 4 * Wq, stream_ptr(c.device)), "dmb_conf_ring_f32")
+        launch("dmb_conf_gather_f32", hq, w2, conf, B, M, Hq, Wq)
+    launch("dmb_conf_ring_f32", cost, comp["w1t"], scale, shift, w2, conf, B, 4 * Dq, M, 4 * Hq, 4 * Wq)
     return conf
 
 
-EPE_WORKSPACE_DOUBLES_PER_IMAGE = 64 * 6   # include/dmb_hip.h: 64 slices x 6 sums per image (and estimate)
+EPE_WORKSPACE_DOUBLES_PER_IMAGE = _lib.DEFINES["DMB_EPE_WORKSPACE_DOUBLES"]   # 64 slices x 6 sums per image (and estimate)
 
 
 def epe_accumulate(est, gt, acc, original_size, lower_bound, upper_bound):
     """acc: float64[6] device tensor updated in place; est/gt: [B, 1, Hp, Wp]."""
-    lib = _lib.load()
     est, gt = _f32c(est, "est_disp"), _f32c(gt, "gt_disp")
     B = est.shape[0]
     Hp, Wp = est.shape[-2:]
@@ -1589,16 +1492,13 @@ def epe_accumulate(est, gt, acc, original_size, lower_bound, upper_bound):
         raise _lib.DmbLibraryError("epe_accumulate: maps must be [B, 1, Hp, Wp] with the original size inside, got %s / %s"
                                    % (tuple(est.shape), (H0, W0)))
     ws = torch.empty((B, EPE_WORKSPACE_DOUBLES_PER_IMAGE), dtype=torch.float64, device=est.device)
-    check(lib.dmb_epe_accum_f64(dev_ptr(est), dev_ptr(gt), dev_ptr(acc), dev_ptr(ws), B, Hp, Wp, int(H0), int(W0),
-                                float(lower_bound), float(upper_bound), stream_ptr(est.device)), "dmb_epe_accum_f64")
+    launch("dmb_epe_accum_f64", est, gt, acc, ws, B, Hp, Wp, H0, W0, lower_bound, upper_bound)
     return acc
 
 
 def epe_accumulate_multi(ests, gt, acc, original_size, lower_bound, upper_bound):
     """``ests``: 1 .. 4 maps [B, 1, Hp, Wp] evaluated against the same ``gt`` in one pass; acc: float64[len(ests), 6] (contiguous
     rows of a device tensor), row i updated from ests[i] exactly as ``epe_accumulate`` would."""
-    import ctypes
-    lib = _lib.load()
     n = len(ests)
     ests = [_f32c(e, "est_disp") for e in ests]
     gt = _f32c(gt, "gt_disp")
@@ -1614,16 +1514,13 @@ def epe_accumulate_multi(ests, gt, acc, original_size, lower_bound, upper_bound)
                                    % (tuple(gt.shape), (H0, W0)))
     ws = torch.empty((n, B, EPE_WORKSPACE_DOUBLES_PER_IMAGE), dtype=torch.float64, device=gt.device)
     PA = ctypes.c_void_p * n
-    check(lib.dmb_epe_accum_multi_f64(n, PA(*[dev_ptr(e).value for e in ests]), dev_ptr(gt), dev_ptr(acc), dev_ptr(ws), B, Hp, Wp,
-                                      int(H0), int(W0), float(lower_bound), float(upper_bound), stream_ptr(gt.device)),
-          "dmb_epe_accum_multi_f64")
+    launch("dmb_epe_accum_multi_f64", n, PA(*[dev_ptr(e).value for e in ests]), gt, acc, ws, B, Hp, Wp, H0, W0, lower_bound, upper_bound)
     return acc
 
 
 # ---------------------------------------------------------------------------------------------- 2-D backbone ops
 def _window_ptr(t, ch_offset):
     """Pointer to channel ``ch_offset`` of batch item 0 of a contiguous [B, C, H, W] tensor."""
-    import ctypes
     dev_ptr(t)  # validates device / dtype / contiguity
     return ctypes.c_void_p(t.data_ptr() + 4 * ch_offset * t.shape[2] * t.shape[3])
 
@@ -1634,8 +1531,7 @@ def pack_conv2d_weights(w):
     w = _f32c(w, "weight")
     Co, Ci, k = w.shape[0], w.shape[1], w.shape[2]
     wp = torch.empty((lib.dmb_conv2d_packed_floats(Co, Ci, k),), dtype=torch.float32, device=w.device)
-    check(lib.dmb_conv2d_pack_weights_f32(dev_ptr(w), dev_ptr(wp), Co, Ci, k, stream_ptr(w.device)),
-          "dmb_conv2d_pack_weights_f32")
+    launch("dmb_conv2d_pack_weights_f32", w, wp, Co, Ci, k)
     return wp
 
 
@@ -1648,7 +1544,6 @@ def conv2d(x, wpack, Co, ksize, stride=1, dilation=1, scale=None, shift=None, re
         coff, Ci = in_window if in_window is not None else (0, x.shape[1])
         return sh.conv2d(x if x.is_contiguous() else x.contiguous(), coff, Ci, wpack, Co, ksize, stride, dilation, scale, shift, residual,
                          res_ch_offset, int(bool(relu)) | _conv_flags(), out, out_ch_offset)
-    lib = _lib.load()
     x = _f32c(x, "x")
     B, Cx, H, W = x.shape
     coff, Ci = in_window if in_window is not None else (0, Cx)
@@ -1660,20 +1555,16 @@ def conv2d(x, wpack, Co, ksize, stride=1, dilation=1, scale=None, shift=None, re
         raise _lib.DmbLibraryError("conv2d: output tensor %s does not fit" % (tuple(out.shape),))
     if residual is not None and (tuple(residual.shape[2:]) != (Ho, Wo) or residual.shape[1] < res_ch_offset + Co):
         raise _lib.DmbLibraryError("conv2d: residual shape %s" % (tuple(residual.shape),))
-    check(lib.dmb_conv2d_f32(_window_ptr(x, coff), dev_ptr(wpack), dev_ptr(scale, allow_none=True),
-                             dev_ptr(shift, allow_none=True),
-                             _window_ptr(residual, res_ch_offset) if residual is not None else None,
-                             _window_ptr(out, out_ch_offset), B, Ci, Co, H, W, ksize, stride, dilation, int(bool(relu)) | _conv_flags(),
-                             Cx, out.shape[1], residual.shape[1] if residual is not None else 0, stream_ptr(x.device)),
-          "dmb_conv2d_f32")
+    launch("dmb_conv2d_f32", _window_ptr(x, coff), wpack, opt(scale), opt(shift),
+           _window_ptr(residual, res_ch_offset) if residual is not None else _lib.NULL, _window_ptr(out, out_ch_offset),
+           B, Ci, Co, H, W, ksize, stride, dilation, int(bool(relu)) | _conv_flags(), Cx, out.shape[1],
+           residual.shape[1] if residual is not None else 0)
     return out
 
 
 def conv2d_k3_multi(jobs, Co):
     """``jobs``: list of (x [B, Ci, H, W_q], wpack, out [B, Ctot_q, H, W_q], out_ch_offset): independent 3x3 stride-1 convolutions
     of one layer shape in ONE launch (csrc/conv2d.hip, MULTI); no affine / residual / ReLU."""
-    import ctypes
-    lib = _lib.load()
     n = len(jobs)
     if n < 1 or n > 6:
         raise _lib.DmbLibraryError("conv2d_k3_multi: 1 .. 6 jobs per launch, got %d" % n)
@@ -1696,45 +1587,38 @@ def conv2d_k3_multi(jobs, Co):
         Ws.append(x.shape[3])
         cts.append(out.shape[1])
     PA, IA = ctypes.c_void_p * n, ctypes.c_int * n
-    check(lib.dmb_conv2d_k3_multi_f32(n, PA(*xs), PA(*ws), PA(*ys), IA(*Ws), IA(*cts), B, Ci, Co, H, stream_ptr(x0.device)),
-          "dmb_conv2d_k3_multi_f32")
+    launch("dmb_conv2d_k3_multi_f32", n, PA(*xs), PA(*ws), PA(*ys), IA(*Ws), IA(*cts), B, Ci, Co, H, device=x0.device)
 
 
 def avgpool2d(x, k, in_window=None):
-    lib = _lib.load()
     x = _f32c(x, "x")
     B, Cx, H, W = x.shape
     coff, C = in_window if in_window is not None else (0, Cx)
     y = torch.empty((B, C, H // k, W // k), dtype=torch.float32, device=x.device)
-    check(lib.dmb_avgpool2d_f32(dev_ptr(x), dev_ptr(y), B, C, H, W, int(k), Cx, coff, stream_ptr(x.device)),
-          "dmb_avgpool2d_f32")
+    launch("dmb_avgpool2d_f32", x, y, B, C, H, W, k, Cx, coff)
     return y
 
 
 def bilinear_ac(x, out_hw, out=None, out_ch_offset=0):
-    lib = _lib.load()
     x = _f32c(x, "x")
     B, C, Hi, Wi = x.shape
     Ho, Wo = out_hw
     if out is None:
         out = torch.empty((B, C, Ho, Wo), dtype=torch.float32, device=x.device)
         out_ch_offset = 0
-    check(lib.dmb_bilinear_ac_f32(dev_ptr(x), dev_ptr(out), B, C, Hi, Wi, Ho, Wo, out.shape[1], out_ch_offset,
-                                  stream_ptr(x.device)), "dmb_bilinear_ac_f32")
+    launch("dmb_bilinear_ac_f32", x, out, B, C, Hi, Wi, Ho, Wo, out.shape[1], out_ch_offset)
     return out
 
 
 def bilinear_scale(x, out_hw, mult=1.0, out=None, out_ch_offset=0):
     """F.interpolate(x, out_hw, mode='bilinear', align_corners=False) * mult."""
-    lib = _lib.load()
     x = _f32c(x, "x")
     B, C, Hi, Wi = x.shape
     Ho, Wo = out_hw
     if out is None:
         out = torch.empty((B, C, Ho, Wo), dtype=torch.float32, device=x.device)
         out_ch_offset = 0
-    check(lib.dmb_bilinear_scale_f32(dev_ptr(x), dev_ptr(out), B, C, Hi, Wi, Ho, Wo, float(mult), out.shape[1],
-                                     out_ch_offset, stream_ptr(x.device)), "dmb_bilinear_scale_f32")
+    launch("dmb_bilinear_scale_f32", x, out, B, C, Hi, Wi, Ho, Wo, mult, out.shape[1], out_ch_offset)
     return out
 
 
@@ -1749,7 +1633,6 @@ def stereo_pad_normalize(src, size=None, mean=None, std=None, window=None, chann
     ``src``: float32 [B, Cs, sh, sw], or the decoder's uint8 [B, sh, sw, Cs] (the first ``channels`` are taken, default
     min(Cs, 3)); ``window`` = (y0, x0, h, w) of the source kept (default: all of it); ``size`` = (th, tw) >= window (default:
     the window's); ``mean`` / ``std``: per-channel sequences (both or neither).  Returns float32 [B, C, th, tw]."""
-    lib = _lib.load()
     if not isinstance(src, torch.Tensor) or not src.is_cuda:
         raise _lib.DmbLibraryError("stereo_pad_normalize: the source must be a GPU tensor (no CPU fallback), got %s"
                                    % (getattr(src, "device", type(src)),))
@@ -1769,11 +1652,9 @@ def stereo_pad_normalize(src, size=None, mean=None, std=None, window=None, chann
     if (mean is None) != (std is None) or (mean is not None and (len(mean) != C or len(std) != C)):
         raise _lib.DmbLibraryError("stereo_pad_normalize: mean and std must both hold %d values" % C)
     y = _out_tensor(out, (B, C, th, tw), src.device, "stereo_pad_normalize")
-    stream_ptr(src.device)     # (validates the device)
-    fn = lib.dmb_stereo_pad_normalize_u8 if u8 else lib.dmb_stereo_pad_normalize_f32
-    check(fn(ctypes.c_void_p(src.data_ptr()), dev_ptr(y), B, C, Cs, sh, sw, y0, x0, h, w, th, tw,
-             host_floats(mean) if mean is not None else None, host_floats(std) if std is not None else None,
-             stream_ptr(src.device)), "dmb_stereo_pad_normalize")
+    # (the source is not FP32 in the _u8 form: its pointer goes as it is, and ``device=`` has the stream validate its device)
+    entry = "dmb_stereo_pad_normalize_u8" if u8 else "dmb_stereo_pad_normalize_f32"
+    launch(entry, ctypes.c_void_p(src.data_ptr()), y, B, C, Cs, sh, sw, y0, x0, h, w, th, tw, opt(mean), opt(std), device=src.device)
     return y
 
 
@@ -1785,7 +1666,6 @@ def _loss_workspace(n, device):
 
 def stereo_focal_loss_fwd(cost, gt, variance, disp_values, lower, upper, start_disp, end_disp, focal_coefficient):
     """Returns (loss_out [2] = (loss, divisor), stats [B, H, W, 2]); ``variance``: float or [B, 1, H, W] tensor."""
-    lib = _lib.load()
     cost, gt = _f32c(cost, "cost"), _f32c(gt, "gt")
     B, D, H, W = cost.shape
     vmap = _f32c(variance, "variance") if torch.is_tensor(variance) else None
@@ -1795,18 +1675,13 @@ def stereo_focal_loss_fwd(cost, gt, variance, disp_values, lower, upper, start_d
                                       tuple(vmap.shape) if vmap is not None else None, len(disp_values)))
     stats = torch.empty((B, H, W, 2), dtype=torch.float32, device=cost.device)
     out = torch.empty((2,), dtype=torch.float32, device=cost.device)
-    check(lib.dmb_stereo_focal_loss_fwd_f32(dev_ptr(cost), dev_ptr(gt), dev_ptr(vmap, allow_none=True),
-                                            1.0 if vmap is not None else float(variance), host_floats(disp_values),
-                                            dev_ptr(stats), dev_ptr(_loss_workspace(B * H * W, cost.device)), dev_ptr(out),
-                                            B, D, H, W, float(lower), float(upper), float(start_disp), float(end_disp),
-                                            float(focal_coefficient), stream_ptr(cost.device)),
-          "dmb_stereo_focal_loss_fwd_f32")
+    launch("dmb_stereo_focal_loss_fwd_f32", cost, gt, opt(vmap), 1.0 if vmap is not None else variance, disp_values, stats,
+           _loss_workspace(B * H * W, cost.device), out, B, D, H, W, lower, upper, start_disp, end_disp, focal_coefficient)
     return out, stats
 
 
 def stereo_focal_loss_bwd(cost, gt, variance, disp_values, stats, loss_out, grad_out, lower, upper, start_disp, end_disp,
                           focal_coefficient, want_grad_variance):
-    lib = _lib.load()
     cost, gt = _f32c(cost, "cost"), _f32c(gt, "gt")
     B, D, H, W = cost.shape
     vmap = _f32c(variance, "variance") if torch.is_tensor(variance) else None
@@ -1817,43 +1692,33 @@ def stereo_focal_loss_bwd(cost, gt, variance, disp_values, stats, loss_out, grad
     gcost = torch.empty_like(cost)
     gvar = torch.empty((B, 1, H, W), dtype=torch.float32, device=cost.device) if (want_grad_variance and vmap is not None) else None
     go = _f32c(grad_out.reshape(1), "grad_out")
-    check(lib.dmb_stereo_focal_loss_bwd_f32(dev_ptr(cost), dev_ptr(gt), dev_ptr(vmap, allow_none=True),
-                                            1.0 if vmap is not None else float(variance), host_floats(disp_values),
-                                            dev_ptr(stats), dev_ptr(loss_out), dev_ptr(go), 1.0, dev_ptr(gcost),
-                                            dev_ptr(gvar, allow_none=True), B, D, H, W, float(lower), float(upper),
-                                            float(start_disp), float(end_disp), float(focal_coefficient),
-                                            stream_ptr(cost.device)), "dmb_stereo_focal_loss_bwd_f32")
+    launch("dmb_stereo_focal_loss_bwd_f32", cost, gt, opt(vmap), 1.0 if vmap is not None else variance, disp_values, stats, loss_out,
+           go, 1.0, gcost, opt(gvar), B, D, H, W, lower, upper, start_disp, end_disp, focal_coefficient)
     return gcost, gvar
 
 
 def map_loss_fwd(x, gt, lower, upper, mode):
-    lib = _lib.load()
     x, gt = _f32c(x, "x"), _f32c(gt, "gt")
     if gt.numel() != x.numel():
         raise _lib.DmbLibraryError("map_loss_fwd: map %s and ground truth %s differ in size" % (tuple(x.shape), tuple(gt.shape)))
     out = torch.empty((2,), dtype=torch.float32, device=x.device)
-    check(lib.dmb_map_loss_fwd_f32(dev_ptr(x), dev_ptr(gt), dev_ptr(_loss_workspace(x.numel(), x.device)), dev_ptr(out),
-                                   x.numel(), float(lower), float(upper), int(mode), stream_ptr(x.device)),
-          "dmb_map_loss_fwd_f32")
+    launch("dmb_map_loss_fwd_f32", x, gt, _loss_workspace(x.numel(), x.device), out, x.numel(), lower, upper, mode)
     return out
 
 
 def map_loss_bwd(x, gt, loss_out, grad_out, lower, upper, mode):
-    lib = _lib.load()
     x, gt = _f32c(x, "x"), _f32c(gt, "gt")
     if gt.numel() != x.numel():
         raise _lib.DmbLibraryError("map_loss_bwd: map %s and ground truth %s differ in size" % (tuple(x.shape), tuple(gt.shape)))
     gx = torch.empty_like(x)
     go = _f32c(grad_out.reshape(1), "grad_out")
-    check(lib.dmb_map_loss_bwd_f32(dev_ptr(x), dev_ptr(gt), dev_ptr(loss_out), dev_ptr(go), 1.0, dev_ptr(gx), x.numel(),
-                                   float(lower), float(upper), int(mode), stream_ptr(x.device)), "dmb_map_loss_bwd_f32")
+    launch("dmb_map_loss_bwd_f32", x, gt, loss_out, go, 1.0, gx, x.numel(), lower, upper, mode)
     return gx
 
 
 # ---------------------------------------------------------------------------------------------- spatial propagation (dmb.ops.spn)
 def spn_gaterecurrent2d(X, G1, G2, G3, horizontal, reverse):
     """dmb/ops/spn/functions/gaterecurrent2dnoind.py:10-24 (forward): the whole scan in one launch (csrc/spn.hip)."""
-    lib = _lib.load()
     X = _f32c(X, "X")
     ts = [_f32c(g, "gate") for g in (G1, G2, G3)]
     for g in ts:
@@ -1862,28 +1727,24 @@ def spn_gaterecurrent2d(X, G1, G2, G3, horizontal, reverse):
         raise _lib.DmbLibraryError("spn: X must be [N, C, H, W], got %s" % (tuple(X.shape),))
     N, C, H, W = X.shape
     out = torch.empty_like(X)
-    check(lib.dmb_spn_gaterecurrent2d_f32(dev_ptr(X), dev_ptr(ts[0]), dev_ptr(ts[1]), dev_ptr(ts[2]), dev_ptr(out), N, C, H, W,
-                                          1 if horizontal else 0, 1 if reverse else 0, stream_ptr(X.device)), "dmb_spn_gaterecurrent2d_f32")
+    launch("dmb_spn_gaterecurrent2d_f32", X, *ts, out, N, C, H, W, 1 if horizontal else 0, 1 if reverse else 0)
     return out
 
 
 def spn_gaterecurrent2d_bwd(X, G1, G2, G3, H_fwd, grad_out, horizontal, reverse):
     """gaterecurrent2dnoind.py:26-44 (backward): (dX, dG1, dG2, dG3)."""
-    lib = _lib.load()
     ops_in = [_f32c(t, "spn operand") for t in (X, G1, G2, G3, H_fwd, grad_out)]
     for t in ops_in[1:]:
         _same_shape(ops_in[0], t, "spn_bwd")
     N, C, H, W = ops_in[0].shape
     outs = [torch.empty_like(ops_in[0]) for _ in range(4)]
-    check(lib.dmb_spn_gaterecurrent2d_bwd_f32(*[dev_ptr(t) for t in ops_in], *[dev_ptr(t) for t in outs], N, C, H, W,
-                                              1 if horizontal else 0, 1 if reverse else 0, stream_ptr(ops_in[0].device)),
-          "dmb_spn_gaterecurrent2d_bwd_f32")
+    launch("dmb_spn_gaterecurrent2d_bwd_f32", *ops_in, *outs, N, C, H, W, 1 if horizontal else 0, 1 if reverse else 0)
     return tuple(outs)
 
 
 # ---------------------------------------------------------------------------------------------- AnyNet (csrc/preact_conv.hip)
-PREACT_POOL, PREACT_RELU_IN, PREACT_RELU_OUT, PREACT_GATE = 0x1, 0x2, 0x4, 0x8   # include/dmb_hip.h: DMB_PREACT_*
-PREACT_MAX_CI, PREACT_MAX_CO = 64, 32
+PREACT_POOL, PREACT_RELU_IN, PREACT_RELU_OUT, PREACT_GATE, PREACT_MAX_CI, PREACT_MAX_CO = (
+    _lib.DEFINES["DMB_PREACT_" + n] for n in ("POOL", "RELU_IN", "RELU_OUT", "GATE", "MAX_CI", "MAX_CO"))
 
 
 def preact_conv(x, w, stride=1, pool=False, pre_scale=None, pre_shift=None, pre_relu=False, post_scale=None, post_shift=None,
@@ -1892,7 +1753,6 @@ def preact_conv(x, w, stride=1, pool=False, pre_scale=None, pre_shift=None, pre_
     launch with the pre-activation prologue and the epilogue of dmb_preact_conv_f32.  ``in_window=(offset, Ci)`` reads channels
     [offset, offset + Ci) of x; ``x2`` (same shape as x) is a second view appended to the batch; ``out`` (optional) is a
     [B (+ B2), Ctot, (D,) Ho, Wo] tensor written at channel ``out_ch_offset``.  ``gate=True`` returns (G1, G2, G3)."""
-    lib = _lib.load()
     x = _f32c(x, "x")
     w = _f32c(w, "weight")
     ndim = x.dim() - 2
@@ -1930,7 +1790,7 @@ def preact_conv(x, w, stride=1, pool=False, pre_scale=None, pre_shift=None, pre_
             raise _lib.DmbLibraryError("preact_conv: gate normalisation needs 3P output channels and its own outputs")
         flags |= PREACT_GATE
         out, *rest = [torch.empty((Bt, Co // 3) + inner, dtype=torch.float32, device=x.device) for _ in range(3)]
-        ys = [dev_ptr(t) for t in rest]
+        ys = rest
         octot, out_ch_offset = Co // 3, 0
     else:
         if out is None:
@@ -1940,19 +1800,14 @@ def preact_conv(x, w, stride=1, pool=False, pre_scale=None, pre_shift=None, pre_
                 or out_ch_offset + Co > out.shape[1]):
             raise _lib.DmbLibraryError("preact_conv: output tensor %s does not fit" % (tuple(out.shape),))
         octot = out.shape[1]
-    check(lib.dmb_preact_conv_f32(dev_ptr(x), dev_ptr(x2, allow_none=True), B, dev_ptr(w),
-                                  dev_ptr(pre_scale, allow_none=True), dev_ptr(pre_shift, allow_none=True),
-                                  dev_ptr(post_scale, allow_none=True), dev_ptr(post_shift, allow_none=True),
-                                  dev_ptr(residual, allow_none=True),
-                                  dev_ptr(out), ys[0], ys[1], Bt, Ci, Co, D, H, W, ndim, int(stride),
-                                  flags, Cx, coff, octot, out_ch_offset, stream_ptr(x.device)), "dmb_preact_conv_f32")
+    launch("dmb_preact_conv_f32", x, opt(x2), B, w, opt(pre_scale), opt(pre_shift), opt(post_scale), opt(post_shift), opt(residual),
+           out, opt(ys[0]), opt(ys[1]), Bt, Ci, Co, D, H, W, ndim, stride, flags, Cx, coff, octot, out_ch_offset)
     return (out, *rest) if gate else out
 
 
 def anynet_stage_samples(low, size, scale, lin=None):
     """models/AnyNet.py:84 / cost_processors/AnyNet.py:64-70: up = F.interpolate(low * scale, size, bilinear,
     align_corners=False) [B, 1, H, W] and, with ``lin`` (device [D]), samples = lin.view(1, D, 1, 1) + up [B, D, H, W]."""
-    lib = _lib.load()
     low = _f32c(low, "low")
     if low.dim() != 4 or low.shape[1] != 1:
         raise _lib.DmbLibraryError("anynet_stage_samples: low must be [B, 1, h, w], got %s" % (tuple(low.shape),))
@@ -1964,40 +1819,34 @@ def anynet_stage_samples(low, size, scale, lin=None):
         lin = _f32c(lin, "lin")
         D = lin.numel()
         samples = torch.empty((B, D, H, W), dtype=torch.float32, device=low.device)
-    check(lib.dmb_anynet_stage_samples_f32(dev_ptr(low), dev_ptr(lin, allow_none=True), dev_ptr(up),
-                                           dev_ptr(samples, allow_none=True), B, h, w, H, W, D, float(scale),
-                                           stream_ptr(low.device)), "dmb_anynet_stage_samples_f32")
+    launch("dmb_anynet_stage_samples_f32", low, opt(lin), up, opt(samples), B, h, w, H, W, D, scale)
     return up, samples
 
 
 def add(a, b):
-    lib = _lib.load()
     a, b = _f32c(a, "a"), _f32c(b, "b")
     _same_shape(a, b, "add")
     c = torch.empty_like(a)
-    check(lib.dmb_add_f32(dev_ptr(a), dev_ptr(b), dev_ptr(c), a.numel(), stream_ptr(a.device)), "dmb_add_f32")
+    launch("dmb_add_f32", a, b, c, a.numel())
     return c
 
 
 def anynet_final_maps(disps, size):
     """models/AnyNet.py:117-118,137-140: the 4 maps ``disps`` [B, 1, h_k, w_k] brought to ``size`` as
     F.interpolate((d * W) / w) and the 3 differences of neighbours, as 7 contiguous [B, 1, H, W] views of one tensor."""
-    lib = _lib.load()
     ds = [_f32c(d, "disp") for d in disps]
     if len(ds) != 4 or any(d.dim() != 4 or d.shape[1] != 1 or d.shape[0] != ds[0].shape[0] for d in ds):
         raise _lib.DmbLibraryError("anynet_final_maps: 4 maps [B, 1, h, w] expected")
     B = ds[0].shape[0]
     H, W = size
     out = torch.empty((7, B, 1, H, W), dtype=torch.float32, device=ds[0].device)
-    check(lib.dmb_anynet_final_maps_f32(*[dev_ptr(d) for d in ds], host_ints([d.shape[2] for d in ds]),
-                                        host_ints([d.shape[3] for d in ds]), dev_ptr(out), B, H, W, stream_ptr(out.device)),
-          "dmb_anynet_final_maps_f32")
+    launch("dmb_anynet_final_maps_f32", *ds, [d.shape[2] for d in ds], [d.shape[3] for d in ds], out, B, H, W)
     return list(out.unbind(0))
 
 
 # ---------------------------------------------------------------------------------------------- DeepPruner's sampler
-PATCH_MATCH_MAX_SAMPLES = 85      # include/dmb_hip.h: DMB_PATCH_MATCH_MAX_SAMPLES
-MAX_DISP_SAMPLES = 256            # include/dmb_hip.h: DMB_MAX_DISP_SAMPLES
+PATCH_MATCH_MAX_SAMPLES = _lib.DEFINES["DMB_PATCH_MATCH_MAX_SAMPLES"]
+MAX_DISP_SAMPLES = _lib.DEFINES["DMB_MAX_DISP_SAMPLES"]
 
 
 def _range_maps(min_disparity, max_disparity, B, H, W, what):
@@ -2018,7 +1867,6 @@ def patch_match_step(left, right, noise, min_disparity=None, max_disparity=None,
     pixel.  Returns (samples, new_noise).  ``out`` None: samples is a new [B, P, H, W]; ``out`` a [B, P + 2, H, W] tensor: the
     samples land in its channels 1 .. P, the range's ends in channels 0 and P + 1, and it is returned.  ``want_noise`` False:
     no new noise is written (the last half-iteration), new_noise is None."""
-    lib = _lib.load()
     left, right = _feature_pair(left, right, "patch_match_step")
     noise = _f32c(noise, "noise")
     B, C, H, W = left.shape
@@ -2039,17 +1887,14 @@ def patch_match_step(left, right, noise, min_disparity=None, max_disparity=None,
             raise _lib.DmbLibraryError("patch_match_step: out must be a contiguous float32 [%d, %d, %d, %d]" % (B, P + 2, H, W))
         ctot, coff, ends = P + 2, 1, 1
     new_noise = torch.empty_like(noise) if want_noise else None
-    check(lib.dmb_patch_match_step_f32(dev_ptr(left), dev_ptr(right), dev_ptr(noise), dev_ptr(lo, allow_none=True),
-                                       dev_ptr(hi, allow_none=True), float(bounds[0]), float(bounds[1]),
-                                       dev_ptr(new_noise, allow_none=True), dev_ptr(res), B, C, P, H, W, int(bool(vertical)),
-                                       float(temperature), ctot, coff, ends, stream_ptr(left.device)), "dmb_patch_match_step_f32")
+    launch("dmb_patch_match_step_f32", left, right, noise, opt(lo), opt(hi), bounds[0], bounds[1], opt(new_noise), res, B, C, P, H, W,
+           int(bool(vertical)), temperature, ctot, coff, ends)
     return res, new_noise
 
 
 def deeppruner_uniform_samples(min_disparity, max_disparity, sample_number, max_disp=None):
     """disp_samplers/DeepPruner.py:99-115: ``sample_number`` samples per pixel, both ends of the range included, [B, N, H, W];
     with ``max_disp`` the range head of stage "post" (:48-66) runs first, in the same launch."""
-    lib = _lib.load()
     lo = _f32c(min_disparity, "min_disparity")
     if lo.dim() != 4 or lo.shape[1] != 1:
         raise _lib.DmbLibraryError("deeppruner_uniform_samples: min_disparity must be [B, 1, H, W], got %s" % (tuple(lo.shape),))
@@ -2057,9 +1902,7 @@ def deeppruner_uniform_samples(min_disparity, max_disparity, sample_number, max_
     lo, hi = _range_maps(lo, max_disparity, B, H, W, "deeppruner_uniform_samples")
     N = int(sample_number)
     out = torch.empty((B, N, H, W), dtype=torch.float32, device=lo.device)
-    check(lib.dmb_deeppruner_uniform_samples_f32(dev_ptr(lo), dev_ptr(hi), dev_ptr(out), B, H, W, N, int(max_disp is not None),
-                                                 float(max_disp if max_disp is not None else 0.0), stream_ptr(lo.device)),
-          "dmb_deeppruner_uniform_samples_f32")
+    launch("dmb_deeppruner_uniform_samples_f32", lo, hi, out, B, H, W, N, max_disp is not None, max_disp if max_disp is not None else 0.0)
     return out
 
 

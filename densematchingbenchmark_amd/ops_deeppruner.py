@@ -9,19 +9,24 @@ No fallback."""
 import torch
 
 from . import _lib
-from .ops import _f32c, _feature_pair, _same_shape, check, dev_ptr, host_ints, stream_ptr
+from ._lib import launch, opt
+from .ops import _f32c, _feature_pair, _same_shape
 
-K5_MAX_C = 16                    # include/dmb_hip.h: DMB_CONV2D_K5_MAX_C
-MAX_FEATURE_PLANES = 85          # include/dmb_hip.h: DMB_PATCH_MATCH_MAX_SAMPLES
-REFINE_HEAD_MAX_C = 16           # include/dmb_hip.h: DMB_REFINE_HEAD_MAX_C
+K5_MAX_C = _lib.DEFINES["DMB_CONV2D_K5_MAX_C"]
+MAX_FEATURE_PLANES = _lib.DEFINES["DMB_PATCH_MATCH_MAX_SAMPLES"]
+REFINE_HEAD_MAX_C = _lib.DEFINES["DMB_REFINE_HEAD_MAX_C"]
 FINAL_MAPS_MAX_K = 3             # include/dmb_hip.h: dmb_deeppruner_final_maps_f32 takes 1 .. 3 list maps
+
+
+def _list_maps(maps):
+    """The FINAL_MAPS_MAX_K pointer slots an entry point has for a list of 1 .. 3 maps: the maps, then NULLs."""
+    return list(maps) + [_lib.NULL] * (FINAL_MAPS_MAX_K - len(maps))
 
 
 def deeppruner_volume(left, right, disp_sample, min_feature=None, max_feature=None):
     """DeepPruner.py:192-195,204-208 in one launch: [B, C, H, W] x 2, samples [B, D, H, W] and, for stage "post", the two range
     feature maps [B, P, H, W] -> [B, 2C + 1 + 2P, D, H, W] = cat(fast_cat_fms(left, right, samples), samples, min_feature on every
     plane, max_feature on every plane), bit for bit, each element written once."""
-    lib = _lib.load()
     left, right = _feature_pair(left, right, "deeppruner_volume")
     B, C, H, W = left.shape
     ds = _f32c(disp_sample, "disp_sample")
@@ -38,16 +43,13 @@ def deeppruner_volume(left, right, disp_sample, min_feature=None, max_feature=No
                                        % (tuple(min_feature.shape),))
         P = min_feature.shape[1]
     out = torch.empty((B, 2 * C + 1 + 2 * P, D, H, W), dtype=torch.float32, device=left.device)
-    check(lib.dmb_deeppruner_volume_f32(dev_ptr(left), dev_ptr(right), dev_ptr(ds), dev_ptr(min_feature, allow_none=True),
-                                        dev_ptr(max_feature, allow_none=True), dev_ptr(out), B, C, D, H, W, P,
-                                        stream_ptr(left.device)), "dmb_deeppruner_volume_f32")
+    launch("dmb_deeppruner_volume_f32", left, right, ds, opt(min_feature), opt(max_feature), out, B, C, D, H, W, P)
     return out
 
 
 def conv2d_k5_small(x, w, scale=None, shift=None, relu=False):
     """nn.Conv2d(Ci, Co, 5, stride 1, padding 2) on 1 .. 16 channels: x [B, Ci, H, W], w [Co, Ci, 5, 5] as it is -> [B, Co, H, W];
     epilogue acc * scale[co] + shift[co] (``scale`` None: acc + shift[co], a bias; both None: acc), then ReLU if ``relu``."""
-    lib = _lib.load()
     x, w = _f32c(x, "x"), _f32c(w, "w")
     if x.dim() != 4 or w.dim() != 4 or tuple(w.shape[1:]) != (x.shape[1], 5, 5):
         raise _lib.DmbLibraryError("conv2d_k5_small: x [B, Ci, H, W] and w [Co, Ci, 5, 5] expected, got %s and %s"
@@ -60,9 +62,7 @@ def conv2d_k5_small(x, w, scale=None, shift=None, relu=False):
     scale = scale.contiguous() if scale is not None else None
     shift = shift.contiguous() if shift is not None else None
     y = torch.empty((B, Co, H, W), dtype=torch.float32, device=x.device)
-    check(lib.dmb_conv2d_k5_small_f32(dev_ptr(x), dev_ptr(w), dev_ptr(scale, allow_none=True), dev_ptr(shift, allow_none=True),
-                                      dev_ptr(y), B, Ci, Co, H, W, 1 if relu else 0, stream_ptr(x.device)),
-          "dmb_conv2d_k5_small_f32")
+    launch("dmb_conv2d_k5_small_f32", x, w, opt(scale), opt(shift), y, B, Ci, Co, H, W, 1 if relu else 0)
     return y
 
 
@@ -70,7 +70,6 @@ def refine_head_up2(x, w, init):
     """The tail of a DeepPruner refinement stage (disp_refinement/DeepPruner.py:36,40-42,87) in one launch: x [B, Ci, H, W]
     (1 <= Ci <= 16), w [1, Ci, 3, 3] as it is, init [B, 1, H, W] -> [B, 1, 2H, 2W] =
     F.interpolate(2 * relu(conv3x3(x, w, padding 1) + init), scale_factor 2, bilinear, align_corners=False)."""
-    lib = _lib.load()
     x, w, init = _f32c(x, "x"), _f32c(w, "w"), _f32c(init, "init")
     if x.dim() != 4 or w.dim() != 4 or tuple(w.shape) != (1, x.shape[1], 3, 3):
         raise _lib.DmbLibraryError("refine_head_up2: x [B, Ci, H, W] and w [1, Ci, 3, 3] expected, got %s and %s"
@@ -81,8 +80,7 @@ def refine_head_up2(x, w, init):
     if tuple(init.shape) != (B, 1, H, W):
         raise _lib.DmbLibraryError("refine_head_up2: init must be [B, 1, H, W] = %s, got %s" % ((B, 1, H, W), tuple(init.shape)))
     y = torch.empty((B, 1, 2 * H, 2 * W), dtype=torch.float32, device=x.device)
-    check(lib.dmb_refine_head_up2_f32(dev_ptr(x), dev_ptr(w), dev_ptr(init), dev_ptr(y), B, Ci, H, W, stream_ptr(x.device)),
-          "dmb_refine_head_up2_f32")
+    launch("dmb_refine_head_up2_f32", x, w, init, y, B, Ci, H, W)
     return y
 
 
@@ -92,7 +90,6 @@ def deeppruner_final_maps(disps, min_disparity, max_disparity, size):
     [B, 1, h, w] brought to ``size`` = (H, W) as up(d) = F.interpolate((d * W) / w_d, size, bilinear, align_corners=False).
     Returns K + 4 contiguous [B, 1, H, W] views of one tensor: up(d_0) .. up(d_{K-1}) = D, (Mn * W) / W, (Mx * W) / W with
     Mn = up(min_disparity) and Mx = up(max_disparity), |D - Mn| and |Mx - D|."""
-    lib = _lib.load()
     ds = [_f32c(d, "disp") for d in disps]
     K = len(ds)
     if K < 1 or K > FINAL_MAPS_MAX_K:
@@ -107,10 +104,8 @@ def deeppruner_final_maps(disps, min_disparity, max_disparity, size):
     if H < 1 or W < 1:
         raise _lib.DmbLibraryError("deeppruner_final_maps: the output size must be positive, got %s" % ((H, W),))
     out = torch.empty((K + 4, B, 1, H, W), dtype=torch.float32, device=ds[0].device)
-    ptrs = [dev_ptr(d) for d in ds] + [None] * (FINAL_MAPS_MAX_K - K)
-    check(lib.dmb_deeppruner_final_maps_f32(*ptrs, host_ints([d.shape[2] for d in ds]), host_ints([d.shape[3] for d in ds]),
-                                            dev_ptr(lo), dev_ptr(hi), dev_ptr(out), K, B, lo.shape[2], lo.shape[3], H, W,
-                                            stream_ptr(out.device)), "dmb_deeppruner_final_maps_f32")
+    launch("dmb_deeppruner_final_maps_f32", *_list_maps(ds), [d.shape[2] for d in ds], [d.shape[3] for d in ds], lo, hi, out, K, B,
+           lo.shape[2], lo.shape[3], H, W)
     return list(out.unbind(0))
 
 
@@ -140,18 +135,13 @@ def deeppruner_loss_fwd(disps, min_disparity, max_disparity, gt, l1_lower, l1_up
     Returns (``out`` [K + 4] float32, ``stats`` [2] float64): the K + 2 smooth-L1 means of up(d_k), (Mn * W) / W and (Mx * W) / W
     under l1_lower < gt < l1_upper (0 for an empty mask), the two quantile means of Mn and Mx under q_lower < gt < q_upper (NaN for
     an empty mask), and the two counts for ``deeppruner_loss_bwd``.  No full-size tensor is written."""
-    lib = _lib.load()
     ds, lo, hi, gt = _loss_operands(disps, min_disparity, max_disparity, gt, theta, "deeppruner_loss_fwd")
     K = len(ds)
     out = torch.empty((K + 4,), dtype=torch.float32, device=gt.device)
     stats = torch.empty((2,), dtype=torch.float64, device=gt.device)
     ws = torch.empty((_lib.DEEPPRUNER_LOSS_WORKSPACE_DOUBLES,), dtype=torch.float64, device=gt.device)
-    ptrs = [dev_ptr(d) for d in ds] + [None] * (FINAL_MAPS_MAX_K - K)
-    check(lib.dmb_deeppruner_loss_fwd_f32(*ptrs, host_ints([d.shape[2] for d in ds]), host_ints([d.shape[3] for d in ds]),
-                                          dev_ptr(lo), dev_ptr(hi), dev_ptr(gt), dev_ptr(ws), dev_ptr(out), dev_ptr(stats), K,
-                                          gt.shape[0], lo.shape[2], lo.shape[3], gt.shape[2], gt.shape[3], float(l1_lower),
-                                          float(l1_upper), float(q_lower), float(q_upper), float(theta), stream_ptr(gt.device)),
-          "dmb_deeppruner_loss_fwd_f32")
+    launch("dmb_deeppruner_loss_fwd_f32", *_list_maps(ds), [d.shape[2] for d in ds], [d.shape[3] for d in ds], lo, hi, gt, ws, out, stats,
+           K, gt.shape[0], lo.shape[2], lo.shape[3], gt.shape[2], gt.shape[3], l1_lower, l1_upper, q_lower, q_upper, theta)
     return out, stats
 
 
@@ -167,20 +157,15 @@ def _loss_stats(stats, grad_out, n, device, what):
 def deeppruner_loss_bwd(disps, min_disparity, max_disparity, gt, stats, grad_out, l1_lower, l1_upper, q_lower, q_upper, theta):
     """Backward of ``deeppruner_loss_fwd`` in one launch: ``grad_out`` [K + 4] on the device (never read on the host), ``stats`` the
     forward's.  Returns ([grad_d0 .. grad_d{K-1}], grad_min, grad_max) with the shapes of the maps, every element written once."""
-    lib = _lib.load()
     ds, lo, hi, gt = _loss_operands(disps, min_disparity, max_disparity, gt, theta, "deeppruner_loss_bwd")
     K = len(ds)
     go = _loss_stats(stats, grad_out, K + 4, gt.device, "deeppruner_loss_bwd")
     gds = [torch.empty(tuple(d.shape), dtype=torch.float32, device=gt.device) for d in ds]
     glo = torch.empty(tuple(lo.shape), dtype=torch.float32, device=gt.device)
     ghi = torch.empty(tuple(hi.shape), dtype=torch.float32, device=gt.device)
-    ptrs = [dev_ptr(d) for d in ds] + [None] * (FINAL_MAPS_MAX_K - K)
-    gptrs = [dev_ptr(g) for g in gds] + [None] * (FINAL_MAPS_MAX_K - K)
-    check(lib.dmb_deeppruner_loss_bwd_f32(*ptrs, host_ints([d.shape[2] for d in ds]), host_ints([d.shape[3] for d in ds]),
-                                          dev_ptr(lo), dev_ptr(hi), dev_ptr(gt), dev_ptr(stats), dev_ptr(go), *gptrs, dev_ptr(glo),
-                                          dev_ptr(ghi), K, gt.shape[0], lo.shape[2], lo.shape[3], gt.shape[2], gt.shape[3],
-                                          float(l1_lower), float(l1_upper), float(q_lower), float(q_upper), float(theta),
-                                          stream_ptr(gt.device)), "dmb_deeppruner_loss_bwd_f32")
+    launch("dmb_deeppruner_loss_bwd_f32", *_list_maps(ds), [d.shape[2] for d in ds], [d.shape[3] for d in ds], lo, hi, gt, stats, go,
+           *_list_maps(gds), glo, ghi, K, gt.shape[0], lo.shape[2], lo.shape[3], gt.shape[2], gt.shape[3], l1_lower, l1_upper, q_lower,
+           q_upper, theta)
     return gds, glo, ghi
 
 
@@ -201,25 +186,19 @@ def quantile_loss_fwd(min_disparity, max_disparity, gt, q_lower, q_upper, theta)
     """The two terms of losses/utils/quantile_loss.py:25-37 on maps at the ground truth's size, [B, 1, H, W] each: returns
     (``out`` [2] float32 = the means of (gt - min) * (theta - [gt - min < 0]) and (gt - max) * ((1 - theta) - [gt - max < 0]) under
     q_lower < gt < q_upper, NaN for an empty mask; ``stats`` [2] float64 for ``quantile_loss_bwd``)."""
-    lib = _lib.load()
     lo, hi, gt = _quantile_operands(min_disparity, max_disparity, gt, theta, "quantile_loss_fwd")
     out = torch.empty((2,), dtype=torch.float32, device=gt.device)
     stats = torch.empty((2,), dtype=torch.float64, device=gt.device)
     ws = torch.empty((_lib.DEEPPRUNER_LOSS_WORKSPACE_DOUBLES,), dtype=torch.float64, device=gt.device)
-    check(lib.dmb_quantile_loss_fwd_f32(dev_ptr(lo), dev_ptr(hi), dev_ptr(gt), dev_ptr(ws), dev_ptr(out), dev_ptr(stats),
-                                        gt.shape[0], gt.shape[2], gt.shape[3], float(q_lower), float(q_upper), float(theta),
-                                        stream_ptr(gt.device)), "dmb_quantile_loss_fwd_f32")
+    launch("dmb_quantile_loss_fwd_f32", lo, hi, gt, ws, out, stats, gt.shape[0], gt.shape[2], gt.shape[3], q_lower, q_upper, theta)
     return out, stats
 
 
 def quantile_loss_bwd(min_disparity, max_disparity, gt, stats, grad_out, q_lower, q_upper, theta):
     """Backward of ``quantile_loss_fwd``: ``grad_out`` [2] on the device; returns (grad_min, grad_max), every element written once."""
-    lib = _lib.load()
     lo, hi, gt = _quantile_operands(min_disparity, max_disparity, gt, theta, "quantile_loss_bwd")
     go = _loss_stats(stats, grad_out, 2, gt.device, "quantile_loss_bwd")
     glo = torch.empty(tuple(gt.shape), dtype=torch.float32, device=gt.device)
     ghi = torch.empty(tuple(gt.shape), dtype=torch.float32, device=gt.device)
-    check(lib.dmb_quantile_loss_bwd_f32(dev_ptr(lo), dev_ptr(hi), dev_ptr(gt), dev_ptr(stats), dev_ptr(go), dev_ptr(glo),
-                                        dev_ptr(ghi), gt.shape[0], gt.shape[2], gt.shape[3], float(q_lower), float(q_upper),
-                                        float(theta), stream_ptr(gt.device)), "dmb_quantile_loss_bwd_f32")
+    launch("dmb_quantile_loss_bwd_f32", lo, hi, gt, stats, go, glo, ghi, gt.shape[0], gt.shape[2], gt.shape[3], q_lower, q_upper, theta)
     return glo, ghi

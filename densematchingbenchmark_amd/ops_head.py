@@ -5,7 +5,8 @@ No fallback."""
 import torch
 
 from . import _lib, ops
-from .ops import _affine_ok, _f32c, _relu_mode, _same_shape, check, dev_ptr, stream_ptr
+from ._lib import launch, opt
+from .ops import _affine_ok, _f32c, _relu_mode, _same_shape
 
 
 # The 32 -> 32 classifier convolution with the 32 -> 1 head inside its launch (include/dmb_hip.h: dmb_conv3d_k3_head_f32): the
@@ -14,12 +15,11 @@ from .ops import _affine_ok, _f32c, _relu_mode, _same_shape, check, dev_ptr, str
 # on by default, and ``set_split_k(False)`` keeps the two separate launches.
 def pack_conv3d_head_weights(w):
     """HeadConv3d weight [1, 32, 3, 3, 3] -> the 16 MFMA A fragments of the fused head."""
-    lib = _lib.load()
     w = _f32c(w, "weight")
     if tuple(w.shape) != (1, 32, 3, 3, 3):
         raise _lib.DmbLibraryError("pack_conv3d_head_weights: weight must be [1, 32, 3, 3, 3], got %s" % (tuple(w.shape),))
     wp = torch.empty((_lib.CONV3D_HEAD_PACKED_FLOATS,), dtype=torch.float32, device=w.device)
-    check(lib.dmb_conv3d_head_pack_weights_f32(dev_ptr(w), dev_ptr(wp), stream_ptr(w.device)), "dmb_conv3d_head_pack_weights_f32")
+    launch("dmb_conv3d_head_pack_weights_f32", w, wp)
     return wp
 
 
@@ -58,9 +58,8 @@ def conv3d_k3_head(x, wpack, head_wpack, scale=None, shift=None, bias=0.0, resid
     ws = torch.empty((wsf,), dtype=torch.float32, device=x.device)
     if ops._kernel_timer is not None:
         ops._kernel_timer.start(tag)
-    check(lib.dmb_conv3d_k3_head_f32(dev_ptr(x), dev_ptr(wpack), dev_ptr(scale, allow_none=True), dev_ptr(shift, allow_none=True),
-                                     dev_ptr(head_wpack), float(bias), dev_ptr(residual, allow_none=True), dev_ptr(y), dev_ptr(ws),
-                                     B, Ci, D, H, W, _relu_mode(relu) | ops._conv_flags(), stream_ptr(x.device)), "dmb_conv3d_k3_head_f32")
+    launch("dmb_conv3d_k3_head_f32", x, wpack, opt(scale), opt(shift), head_wpack, bias, opt(residual), y, ws, B, Ci, D, H, W,
+           _relu_mode(relu) | ops._conv_flags())
     if ops._kernel_timer is not None:
         ops._kernel_timer.stop(tag)
     return y

@@ -48,7 +48,9 @@ extern "C" {
  * skip operand already holds (`dres_acc`); 7: DMB_CONV_SINGLE_CHAIN in the `relu` argument of the convolution
  * entry points, `flags` argument of dmb_conv3d_k3_c1_f32; 6: dmb_stereo_pad_normalize_f32 / _u8 added; 5: dmb_fast_fms_bwd_f32 takes a mode, the forward's norm and an
  * optional gradient buffer for per-pixel samples; 4: workspace argument of dmb_deconv3d_k3s2_f32, the merged-heads entry
- * points of version 3 removed). */
+ * points of version 3 removed).  The define is the one place the number is written: dmb_abi_version() returns it and the Python
+ * binding reads it from this file. */
+#define DMB_ABI_VERSION 10
 int dmb_abi_version(void);
 /* Static string describing the last DMB_E* code returned on this thread ("" if none). */
 const char* dmb_last_error(void);

@@ -138,7 +138,7 @@ def test_entry_points_validate_before_any_device_call():
     for Co in (8, 128, 256, 1, 48):
         assert lib.dmb_deconv3d_k3_hw_f32(p, p, None, None, None, p, 1, 32, Co, 4, 4, 4, 0, None) == 100002, Co
     assert b"deconv3d_hw" in lib.dmb_last_error()
-    assert lib.dmb_abi_version() == 10
+    assert lib.dmb_abi_version() == _lib.ABI_VERSION
     del keep
 
 

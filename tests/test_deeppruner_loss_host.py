@@ -41,7 +41,7 @@ def test_import_paths_and_signatures():
     assert list(inspect.signature(DeepPrunerLoss.__call__).parameters) == ["self", "disps", "min_disparity", "max_disparity", "target"]
     for fn in ("deeppruner_loss_fwd", "deeppruner_loss_bwd", "quantile_loss_fwd", "quantile_loss_bwd"):
         src = inspect.getsource(getattr(ops_deeppruner, fn))
-        assert not hasattr(ops, fn) and "check(lib.dmb_" in src and "torch.empty(" in src and "empty_like" not in src and "new_empty" not in src
+        assert not hasattr(ops, fn) and 'launch("dmb_' in src and "torch.empty(" in src and "empty_like" not in src and "new_empty" not in src
     assert ops_deeppruner.torch is torch
 
 
@@ -197,7 +197,7 @@ def test_header_table_abi_and_registries():
     from densematchingbenchmark_amd.modeling.stereo.losses import builder, make_gsm_loss_evaluator
     assert set(_lib.header_symbols()) == set(_lib.SIGNATURES) and all(n in _lib.SIGNATURES for n in NEW)
     lib = _lib.load()
-    assert all(hasattr(lib, n) for n in NEW) and lib.dmb_abi_version() == 10 == _lib.ABI_VERSION
+    assert all(hasattr(lib, n) for n in NEW) and lib.dmb_abi_version() == _lib.ABI_VERSION
     header = open(_lib.HEADER_PATH).read()
     assert "#define DMB_DEEPPRUNER_LOSS_WORKSPACE_DOUBLES %d\n" % _lib.DEEPPRUNER_LOSS_WORKSPACE_DOUBLES in header
     assert set(PROCESSORS) == {'Difference', 'Concatenation', 'Correlation'}

@@ -82,9 +82,9 @@ def test_registries_stay_as_they_were():
     # the new launching wrapper lives next to ops, not in it, and allocates through the module's own ``torch``
     assert not hasattr(ops, "deeppruner_final_maps") and ops_deeppruner.torch is torch
     src = inspect.getsource(ops_deeppruner.deeppruner_final_maps)
-    assert "check(lib.dmb_" in src and "torch.empty(" in src and "empty_like" not in src and "new_empty" not in src
+    assert 'launch("dmb_' in src and "torch.empty(" in src and "empty_like" not in src and "new_empty" not in src
     assert set(_lib.header_symbols()) == set(_lib.SIGNATURES) and "dmb_deeppruner_final_maps_f32" in _lib.SIGNATURES
-    assert _lib.load().dmb_abi_version() == 10 == _lib.ABI_VERSION
+    assert _lib.load().dmb_abi_version() == _lib.ABI_VERSION
 
 
 def test_refusals_come_before_any_launch(monkeypatch):
@@ -225,7 +225,7 @@ def test_entry_point_validates_before_any_device_call():
         assert call(**change) == code, change
         assert b"deeppruner_final_maps" in lib.dmb_last_error(), change
     assert call(K=2, d1=None) == EINVAL and call(K=1, d0=None) == EINVAL       # a NULL among the K maps the list holds
-    assert lib.dmb_abi_version() == 10 == _lib.ABI_VERSION
+    assert lib.dmb_abi_version() == _lib.ABI_VERSION
     del keep
 
 

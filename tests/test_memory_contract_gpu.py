@@ -931,7 +931,7 @@ def _epe_multi(ops, c, shape, original):
 
 # ================================================================================================ the harness
 def launching_wrappers():
-    """Every public function of ``ops`` whose source launches a library kernel: through the ctypes table (directly, or by naming the
+    """Every public function of ``ops`` whose source launches a library kernel: through ``_lib.launch`` (directly, or by naming the
     entry point to the 3-D unit convolutions' shared launch body, ops._unit_conv3d) or through the shim."""
     ops = _ops()
     names = []
@@ -939,7 +939,7 @@ def launching_wrappers():
         if name.startswith("_") or not inspect.isfunction(fn) or fn.__module__ != ops.__name__:
             continue
         src = inspect.getsource(fn)
-        if "check(lib.dmb_" in src or "_unit_conv3d(lib.dmb_" in src or re.search(r"\bsh\.\w+\(", src):
+        if 'launch("dmb_' in src or "_unit_conv3d(lib.dmb_" in src or re.search(r"\bsh\.\w+\(", src):
             names.append(name)
     return sorted(names)
 
