@@ -159,10 +159,14 @@ __device__ __forceinline__ void catconv_combine_body(const float* __restrict__ F
   auto plane = [&](int z, const float4& fvv, const float (&g)[4], const float4& bd, float gbz) {
     float f[4] = {fvv.x, fvv.y, fvv.z, fvv.w};
     if (NEAR) {
+      // the band word as four VALUES: a conditional expression on the members themselves is an lvalue -- a select of addresses
+      // into the block's band array and one load through it, which kept that array in scratch memory (64 bytes per thread written
+      // per block and read back per element: 2.1 x the kernel's output bytes of write traffic)
+      const float b0 = bd.x, b1 = bd.y, b2 = bd.z, b3 = bd.w;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int u = x + e - z;
-        const float t = u == -2 ? bd.x : (u == -1 ? bd.y : (u == 0 ? bd.z : bd.w));
+        const float t = u == -2 ? +b0 : (u == -1 ? +b1 : (u == 0 ? +b2 : +b3));
         f[e] = u >= 2 ? f[e] : (u >= -2 ? t : 0.f);
       }
     }

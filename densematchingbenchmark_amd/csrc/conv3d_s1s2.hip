@@ -104,7 +104,7 @@ struct S1Cfg {
 
 // HEAD: the 48 x 4 row-pair tile of the 32 -> 32 classifier convolution with the 32 -> 1 head that follows it (PSMNet.py:46-54)
 // inside its epilogue; see conv3d_s1_kernel.  Each workgroup leaves the head's partial sums over its own 4 x 4 x 48 voxels: a
-// 6 x 6 x 50 tile (the voxels + the one-voxel halo their taps reach), summed over overlapping tiles by conv3d_head_finish_kernel.
+// 6 x 6 x 50 tile (the voxels + the one-voxel halo their taps reach), summed over overlapping tiles by conv3d_head_chain_finish_kernel.
 struct S1HeadCfg : S1Cfg<0, 32, 4, 48, 2, 1, 1, 16, 0> {
   static constexpr bool HEAD = true;
   static constexpr int OZ = TZ + 2, OY = TY + 2, OX = TX + 2;
@@ -286,7 +286,7 @@ __global__ __launch_bounds__(256, C::WPE) void conv3d_s1_kernel(const float* __r
     // per dz, in which wave wz adds into plane wz + 2 - dz -- no two waves share a plane -- tap by tap, the two lane halves one
     // after the other (they hold different taps and may meet at an address; the 32 lanes of a half never do).
     // Every element so receives its terms in one fixed order.  `y` = the workspace: slot `tile` takes the 1800 partial sums,
-    // contributions to voxels outside the volume included (conv3d_head_finish_kernel drops them).
+    // contributions to voxels outside the volume included (conv3d_head_chain_finish_kernel drops them).
     float* ot = lds;                               // [OZ][OY][OP]
     float* tab = lds + C::OZ * C::OPLANE;          // [h][r]: scale, shift of channel cd_row(r, h)
     float aw[16];
@@ -517,42 +517,108 @@ __global__ void pack_head_weights_kernel(const float* __restrict__ w, float* __r
   whp[i] = tap < 27 ? w[cd_row(s, lane >> 5) * 27 + tap] : 0.f;
 }
 
-// cost[v] = the partial sums of the (at most eight) tiles whose 6 x 6 x 50 slot covers v, added in ascending tile order, + bias
-// (+ residual).  One voxel per thread: a voxel inside a tile reads one float, one on a tile face two, ... a corner eight.
-__global__ __launch_bounds__(256) void conv3d_head_finish_kernel(const float* __restrict__ ws, const float* __restrict__ res,
-                                                                 float* __restrict__ y, float bias, int D, int H, int W, int ntx,
-                                                                 int nty, int ntz, long long total) {
+// The pass that finishes a CHAIN of N <= 4 fused heads (PSMNet.py:70-72: cost_k = classif_k(out_k) + cost_{k-1}) in one launch:
+//   c_1[v] = (the partial sums of the at most eight tiles of ws_1 whose 6 x 6 x 50 slot covers v, in ascending tile order) + b_1 (+ res[v])
+//   c_k[v] = ((the same sum over ws_k) + b_k) + c_{k-1}[v]
+// -- per level the additions of a finishing pass of its own, in their order; c_{k-1} stays in registers instead of being read back.
+// A thread owns four consecutive x of one row: TX % 4 == 0, so they lie in one tile and a slot row holds them as 16 contiguous
+// bytes (ox = lx + 1 .. lx + 4); only the first column of a tile has a term in the left neighbour's slot (ox = OX - 1) and only the
+// last column one in the right neighbour's (ox = 0).  Along z and y a voxel is covered by its own tile and, on the tile's first /
+// last plane or row, by ONE neighbour: two candidates per axis, ascending.  All loads of all levels are issued before the first
+// addition (N independent groups per thread).  VEC: y and res are 16-byte aligned (4-byte otherwise: dword accesses).
+struct HeadChain {
+  const float* ws[4];
+  float* y[4];
+  float bias[4];
+};
+struct __attribute__((packed, aligned(4))) HeadQuad {
+  float v[4];
+};
+
+template <int N, bool VEC>
+__global__ __launch_bounds__(256) void conv3d_head_chain_finish_kernel(HeadChain ch, const float* __restrict__ res, int D, int H, int W,
+                                                                       int ntx, int nty, int ntz, long long groups) {
   using C = S1HeadCfg;
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  const int gx = (int)(idx % W);
-  long long q = idx / W;
+  static_assert(C::TX % 4 == 0 && C::OZ == C::TZ + 2 && C::OY == C::TY + 2 && C::OX == C::TX + 2, "four columns of a thread share a tile");
+  const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (g >= groups) return;
+  const int W4 = W / 4;
+  const int gx = (int)(g % W4) * 4;
+  long long q = g / W4;
   const int gy = (int)(q % H);
   q /= H;
   const int gz = (int)(q % D), b = (int)(q / D);
   const int tz = gz / C::TZ, ty = gy / C::TY, tx = gx / C::TX;
   const int lz = gz - tz * C::TZ, ly = gy - ty * C::TY, lx = gx - tx * C::TX;
-  float s = 0.f;
-  bool any = false;
-  for (int a = -1; a <= 1; ++a) {
-    const int oz = lz - a * C::TZ + 1;   // where tile tz + a keeps this plane
-    if (oz < 0 || oz >= C::OZ || tz + a < 0 || tz + a >= ntz) continue;
-    for (int c = -1; c <= 1; ++c) {
-      const int oy = ly - c * C::TY + 1;
-      if (oy < 0 || oy >= C::OY || ty + c < 0 || ty + c >= nty) continue;
-      for (int e = -1; e <= 1; ++e) {
-        const int ox = lx - e * C::TX + 1;
-        if (ox < 0 || ox >= C::OX || tx + e < 0 || tx + e >= ntx) continue;
-        const size_t slot = (((size_t)b * ntz + (tz + a)) * nty + (ty + c)) * ntx + (tx + e);
-        const float v = ws[slot * C::OUT_FLOATS + (oz * C::OY + oy) * C::OX + ox];
-        s = any ? s + v : v;
-        any = true;
-      }
+  // candidate 0 / 1 per axis: (tile, plane or row inside its slot); candidate 0 always exists
+  const bool zlo = lz == 0 && tz > 0, zhi = lz == C::TZ - 1 && tz + 1 < ntz;
+  const bool ylo = ly == 0 && ty > 0, yhi = ly == C::TY - 1 && ty + 1 < nty;
+  const int zt[2] = {zlo ? tz - 1 : tz, zlo ? tz : tz + 1}, zo[2] = {zlo ? C::TZ + 1 : lz + 1, zlo ? 1 : 0};
+  const int yt[2] = {ylo ? ty - 1 : ty, ylo ? ty : ty + 1}, yo[2] = {ylo ? C::TY + 1 : ly + 1, ylo ? 1 : 0};
+  const bool zv = zlo || zhi, yv = ylo || yhi;
+  const bool left = lx == 0 && tx > 0, right = lx == C::TX - 4 && tx + 1 < ntx;
+  bool valid[4];
+  size_t at[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    valid[i] = ((i >> 1) == 0 || zv) && ((i & 1) == 0 || yv);
+    const size_t slot = (((size_t)b * ntz + zt[i >> 1]) * nty + yt[i & 1]) * ntx + tx;
+    at[i] = slot * C::OUT_FLOATS + (zo[i >> 1] * C::OY + yo[i & 1]) * C::OX;
+  }
+  HeadQuad own[N][4];
+  float lf[N][4], rt[N][4];
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const float* __restrict__ ws = ch.ws[k];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (!valid[i]) continue;
+      own[k][i] = *reinterpret_cast<const HeadQuad*>(ws + at[i] + lx + 1);
+      if (left) lf[k][i] = ws[at[i] - C::OUT_FLOATS + C::OX - 1];
+      if (right) rt[k][i] = ws[at[i] + C::OUT_FLOATS];
     }
   }
-  s += bias;
-  if (res) s += res[idx];
-  y[idx] = s;
+  const size_t idx = (size_t)g * 4;
+  float s[4] = {0.f, 0.f, 0.f, 0.f};   // c_{k-1}
+  if (res) {
+    if constexpr (VEC) {
+      const float4 r = *reinterpret_cast<const float4*>(res + idx);
+      s[0] = r.x, s[1] = r.y, s[2] = r.z, s[3] = r.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[j] = res[idx + j];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    float t[4];
+    // candidate 0 (always there): the left neighbour's term, if any, comes first
+    t[0] = left ? lf[k][0] + own[k][0].v[0] : own[k][0].v[0];
+    t[1] = own[k][0].v[1];
+    t[2] = own[k][0].v[2];
+    t[3] = right ? own[k][0].v[3] + rt[k][0] : own[k][0].v[3];
+#pragma unroll
+    for (int i = 1; i < 4; ++i) {
+      if (!valid[i]) continue;
+      if (left) t[0] += lf[k][i];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t[j] += own[k][i].v[j];
+      if (right) t[3] += rt[k][i];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      t[j] += ch.bias[k];
+      if (k > 0 || res) t[j] += s[j];
+      s[j] = t[j];
+    }
+    float* __restrict__ y = ch.y[k];
+    if constexpr (VEC) {
+      *reinterpret_cast<float4*>(y + idx) = make_float4(s[0], s[1], s[2], s[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) y[idx + j] = s[j];
+    }
+  }
 }
 
 template <class C>
@@ -1173,11 +1239,12 @@ extern "C" int dmb_conv3d_head_pack_weights_f32(const float* w, float* wpack, vo
   hipLaunchKernelGGL(pack_head_weights_kernel, dim3(HEAD_PACKED_FLOATS / 256), dim3(256), 0, (hipStream_t)stream, w, wpack);
   return launch_status("conv3d_head_pack_weights launch failed");
 }
-extern "C" int dmb_conv3d_k3_head_f32(const float* x, const float* wpack, const float* scale, const float* shift,
-                                      const float* head_wpack, float bias, const float* residual, float* y, float* workspace,
-                                      int B, int Ci, int D, int H, int W, int relu, void* stream) {
+// first half: the convolution launch; slot `tile` of the workspace takes that workgroup's 6 x 6 x 50 partial sums
+extern "C" int dmb_conv3d_k3_head_partial_f32(const float* x, const float* wpack, const float* scale, const float* shift,
+                                              const float* head_wpack, float* workspace, int B, int Ci, int D, int H, int W, int relu,
+                                              void* stream) {
   using C = S1HeadCfg;
-  if (!x || !wpack || !head_wpack || !y || !workspace || B <= 0 || Ci <= 0 || D <= 0 || H <= 0 || W <= 0)
+  if (!x || !wpack || !head_wpack || !workspace || B <= 0 || Ci <= 0 || D <= 0 || H <= 0 || W <= 0)
     return fail(DMB_EINVAL, "conv3d_head: bad argument");
   if (relu & DMB_CONV_SINGLE_CHAIN) return fail(DMB_EUNSUPPORTED, "conv3d_head: not a single-chain sum (use dmb_conv3d_k3_f32 + dmb_conv3d_k3_c1_f32)");
   relu &= 0xff;
@@ -1185,15 +1252,57 @@ extern "C" int dmb_conv3d_k3_head_f32(const float* x, const float* wpack, const 
     return fail(DMB_EUNSUPPORTED, "conv3d_head: 16-byte rows only (W % 4 == 0, x 16-byte aligned, 32 channels of one batch item below 2 GiB), workspace 8-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const int ntx = cdiv(W, C::TX), nty = cdiv(H, C::TY), ntz = cdiv(D, C::TZ);
-  const long long nblk = (long long)B * ntx * nty * ntz, total = (long long)B * D * H * W;
-  if (nblk > 0x7fffffffLL || cdiv_ll(total, 256) > 0x7fffffffLL) return fail(DMB_EUNSUPPORTED, "conv3d_head: grid too large");
+  const long long nblk = (long long)B * ntx * nty * ntz;
+  if (nblk > 0x7fffffffLL) return fail(DMB_EUNSUPPORTED, "conv3d_head: grid too large");
   const size_t lds = (size_t)C::LDS_FLOATS * sizeof(float);
   DMB_ENSURE_LDS((&conv3d_s1_kernel<C, false>), (size_t)(lds));
   hipLaunchKernelGGL((conv3d_s1_kernel<C, false>), dim3((unsigned)nblk), dim3(256), lds, st, x, wpack, scale, shift, head_wpack,
                      workspace, Ci, D, H, W, ntx, nty, ntz, relu, (double*)nullptr);
-  const int rc = launch_status("conv3d_head launch failed");
-  if (rc != DMB_OK) return rc;
-  hipLaunchKernelGGL(conv3d_head_finish_kernel, dim3((unsigned)cdiv_ll(total, 256)), dim3(256), 0, st, workspace, residual, y, bias, D,
-                     H, W, ntx, nty, ntz, total);
+  return launch_status("conv3d_head launch failed");
+}
+
+// second half: one finishing pass over the workspaces of a chain of heads (conv3d_head_chain_finish_kernel)
+template <int N>
+static void launch_head_chain(const HeadChain& ch, const float* res, bool vec, int D, int H, int W, int ntx, int nty, int ntz,
+                              long long groups, hipStream_t st) {
+  const dim3 grid((unsigned)cdiv_ll(groups, 256));
+  if (vec)
+    hipLaunchKernelGGL((conv3d_head_chain_finish_kernel<N, true>), grid, dim3(256), 0, st, ch, res, D, H, W, ntx, nty, ntz, groups);
+  else
+    hipLaunchKernelGGL((conv3d_head_chain_finish_kernel<N, false>), grid, dim3(256), 0, st, ch, res, D, H, W, ntx, nty, ntz, groups);
+}
+extern "C" int dmb_conv3d_head_chain_finish_f32(int nlevels, const float* const* workspaces, const float* bias_host,
+                                                const float* residual, float* const* y, int B, int D, int H, int W, void* stream) {
+  using C = S1HeadCfg;
+  if (nlevels < 1 || nlevels > 4 || !workspaces || !bias_host || !y || B <= 0 || D <= 0 || H <= 0 || W <= 0)
+    return fail(DMB_EINVAL, "conv3d_head_chain_finish: bad argument (1 .. 4 levels)");
+  if (!s1_head_runs(B, D, H, W)) return fail(DMB_EUNSUPPORTED, "conv3d_head_chain_finish: 16-byte rows only (W % 4 == 0, 32 channels of one batch item below 2 GiB)");
+  HeadChain ch{};
+  bool vec = (((uintptr_t)residual) & 15) == 0;
+  for (int k = 0; k < nlevels; ++k) {
+    if (!workspaces[k] || !y[k]) return fail(DMB_EINVAL, "conv3d_head_chain_finish: NULL workspace or output");
+    ch.ws[k] = workspaces[k], ch.y[k] = y[k], ch.bias[k] = bias_host[k];
+    vec = vec && (((uintptr_t)y[k]) & 15) == 0;
+  }
+  const int ntx = cdiv(W, C::TX), nty = cdiv(H, C::TY), ntz = cdiv(D, C::TZ);
+  const long long groups = (long long)B * D * H * (W / 4);
+  if (cdiv_ll(groups, 256) > 0x7fffffffLL) return fail(DMB_EUNSUPPORTED, "conv3d_head_chain_finish: grid too large");
+  hipStream_t st = (hipStream_t)stream;
+  switch (nlevels) {
+    case 1: launch_head_chain<1>(ch, residual, vec, D, H, W, ntx, nty, ntz, groups, st); break;
+    case 2: launch_head_chain<2>(ch, residual, vec, D, H, W, ntx, nty, ntz, groups, st); break;
+    case 3: launch_head_chain<3>(ch, residual, vec, D, H, W, ntx, nty, ntz, groups, st); break;
+    default: launch_head_chain<4>(ch, residual, vec, D, H, W, ntx, nty, ntz, groups, st); break;
+  }
   return launch_status("conv3d_head finishing launch failed");
+}
+
+extern "C" int dmb_conv3d_k3_head_f32(const float* x, const float* wpack, const float* scale, const float* shift,
+                                      const float* head_wpack, float bias, const float* residual, float* y, float* workspace,
+                                      int B, int Ci, int D, int H, int W, int relu, void* stream) {
+  if (!y) return fail(DMB_EINVAL, "conv3d_head: bad argument");
+  const int rc = dmb_conv3d_k3_head_partial_f32(x, wpack, scale, shift, head_wpack, workspace, B, Ci, D, H, W, relu, stream);
+  if (rc != DMB_OK) return rc;
+  const float* ws = workspace;
+  return dmb_conv3d_head_chain_finish_f32(1, &ws, &bias, residual, &y, B, D, H, W, stream);
 }

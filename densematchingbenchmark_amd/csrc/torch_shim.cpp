@@ -142,6 +142,47 @@ at::Tensor conv3d_k3_head(const at::Tensor& x, const at::Tensor& wpack, const c1
   return y;
 }
 
+// ---- dmb_conv3d_k3_head_partial_f32 / dmb_conv3d_head_chain_finish_f32: the two halves of the call above -------------------------
+at::Tensor conv3d_k3_head_partial(const at::Tensor& x, const at::Tensor& wpack, const c10::optional<at::Tensor>& scale,
+                                  const c10::optional<at::Tensor>& shift, const at::Tensor& head_wpack, int64_t relu_flags) {
+  f32(x, "x");
+  if (x.dim() != 5) raise("conv3d_k3_head_partial: x must be [B, Ci, D, H, W]");
+  const int64_t B = x.size(0), Ci = x.size(1), D = x.size(2), H = x.size(3), W = x.size(4);
+  affine_ok(scale, shift, 32, "conv3d_k3_head_partial");
+  if (wpack.numel() != dmb_conv3d_packed_floats(32, (int)Ci)) raise("conv3d_k3_head_partial: packed weights do not belong to these channel counts");
+  if (head_wpack.numel() != DMB_CONV3D_HEAD_PACKED_FLOATS) raise("conv3d_k3_head_partial: head weights must come from conv3d_head_pack_weights");
+  const long long wsf = dmb_conv3d_k3_head_workspace_floats((int)B, (int)D, (int)H, (int)W);
+  if (wsf <= 0) raise("conv3d_k3_head_partial: this shape does not take the fused form (use conv3d_k3 + conv3d_k3_c1)");
+  at::Tensor ws = at::empty({(int64_t)wsf}, x.options());
+  chk(dmb_conv3d_k3_head_partial_f32(ptr(x, "x"), ptr(wpack, "wpack"), optr(scale, "scale"), optr(shift, "shift"), ptr(head_wpack, "head_wpack"),
+                                     ws.data_ptr<float>(), (int)B, (int)Ci, (int)D, (int)H, (int)W, (int)relu_flags, stream_of(x)),
+      "dmb_conv3d_k3_head_partial_f32");
+  return ws;
+}
+
+// workspaces of one [B, ., D, H, W] shape -> y [N, B, 1, D, H, W], level k in y[k]
+at::Tensor conv3d_head_chain_finish(const std::vector<at::Tensor>& workspaces, const std::vector<double>& bias,
+                                    const c10::optional<at::Tensor>& residual, int64_t B, int64_t D, int64_t H, int64_t W) {
+  const int64_t N = (int64_t)workspaces.size();
+  if (N < 1 || N > 4 || (int64_t)bias.size() != N) raise("conv3d_head_chain_finish: 1 .. 4 workspaces and one bias per workspace");
+  const long long wsf = dmb_conv3d_k3_head_workspace_floats((int)B, (int)D, (int)H, (int)W);
+  if (wsf <= 0) raise("conv3d_head_chain_finish: this shape does not take the fused form");
+  const float* wsp[4];
+  float* yp[4];
+  float bs[4];
+  at::Tensor y = at::empty({N, B, 1, D, H, W}, workspaces[0].options());
+  for (int64_t k = 0; k < N; ++k) {
+    if (workspaces[k].numel() != wsf || workspaces[k].device() != y.device()) raise("conv3d_head_chain_finish: a workspace does not belong to this shape");
+    wsp[k] = ptr(workspaces[k], "workspace");
+    yp[k] = y.data_ptr<float>() + k * B * D * H * W;
+    bs[k] = (float)bias[k];
+  }
+  if (residual.has_value() && (residual->numel() != B * D * H * W || residual->device() != y.device())) raise("conv3d_head_chain_finish residual: shapes differ");
+  chk(dmb_conv3d_head_chain_finish_f32((int)N, wsp, bs, optr(residual, "residual"), yp, (int)B, (int)D, (int)H, (int)W, stream_of(y)),
+      "dmb_conv3d_head_chain_finish_f32");
+  return y;
+}
+
 // ---- dmb_trilinear_ac_soft_argmin_f32 (aggregators/PSMNet.py:74-93 + disp_predictors/faster_soft_argmin.py:46-71) -----------------
 std::vector<at::Tensor> trilinear_ac_soft_argmin(const at::Tensor& x, int64_t Do, int64_t Ho, int64_t Wo, double alpha,
                                                  const std::vector<float>& disp_values) {
@@ -315,6 +356,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("deconv3d_k3s2", &deconv3d_k3s2);
   m.def("conv3d_k3_c1", &conv3d_k3_c1);
   m.def("conv3d_k3_head", &conv3d_k3_head);
+  m.def("conv3d_k3_head_partial", &conv3d_k3_head_partial);
+  m.def("conv3d_head_chain_finish", &conv3d_head_chain_finish);
   m.def("trilinear_ac_soft_argmin", &trilinear_ac_soft_argmin);
   m.def("conv2d", &conv2d);
   m.def("copy_window", &copy_window);

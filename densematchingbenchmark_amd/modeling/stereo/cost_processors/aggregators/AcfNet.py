@@ -12,6 +12,8 @@ class AcfAggregator(PSMAggregator):
     """Same trunk wiring as PSMAggregator but dres0/dres1/classif*.0 convs carry a bias (AcfNet.py:31-52 omit
     ``bias=False``) and the up-sampling is three learned ConvTranspose3d(1, 1, 8, 4, 2) (AcfNet.py:55-57,81-83)."""
 
+    chain_heads = False       # each level feeds a learned up-sampling of its own: one fused head call per level, as before
+
     def __init__(self, max_disp, in_planes=64, batch_norm=True):
         nn.Module.__init__(self)
         self.max_disp, self.in_planes, self.batch_norm = max_disp, in_planes, batch_norm

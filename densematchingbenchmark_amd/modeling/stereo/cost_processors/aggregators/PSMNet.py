@@ -4,16 +4,18 @@ import torch.nn as nn
 
 from ..... import ops
 from ...layers import train_fn
-from ...layers.basic_layers import HeadConv3d, classifier_branch, conv3d_bn, conv3d_bn_relu
+from ...layers.basic_layers import HeadConv3d, classifier_branch, classifier_chain, conv3d_bn, conv3d_bn_relu
 from ..utils.hourglass import Hourglass
 
 
 class PSMAggregator(nn.Module):
     """raw_cost [B, in_planes, D/4, H/4, W/4] -> [cost3, cost2, cost1], each [B, max_disp, H, W] (best first).
     25 fused MFMA conv launches + 3 head convs + 3 trilinear up-samplings; all biases absent (PSMNet.py:31-54).  In eval mode the
-    three classifier convolutions carry their head inside their own launch where ``classifier_branch`` allows it."""
+    three classifier convolutions carry their head inside their own launch where ``classifier_branch`` allows it; their three
+    finishing passes are then one (``classifier_chain``)."""
 
     accepts_lazy_cat = True   # dres0[0] is a FusedConv3d: it takes a LazyCatVolume (cost_processors/utils/cat_fms.py)
+    chain_heads = True        # eval: one finishing pass for the three levels (False: one per level)
 
     def __init__(self, max_disp, in_planes=64, batch_norm=True):
         super().__init__()
@@ -37,6 +39,12 @@ class PSMAggregator(nn.Module):
         out1, pre1, post1 = self.dres2(cost0, None, None, skip=cost0)    # out1 + cost0 fused into conv6
         out2, pre2, post2 = self.dres3(out1, pre1, post1, skip=cost0)
         out3, pre3, post3 = self.dres4(out2, pre2, post2, skip=cost0)
+        if self.chain_heads:
+            # eval mode, every branch in its fused form: three convolution launches into three workspaces, then ONE finishing
+            # pass for the three costs (same bits); the levels come back as the parts of one [3, B, 1, D, H, W] buffer
+            costs = classifier_chain([tuple(self.classif1), tuple(self.classif2), tuple(self.classif3)], [out1, out2, out3])
+            if costs is not None:
+                return costs
         cost1 = classifier_branch(self.classif1[0], self.classif1[1], out1)
         cost2 = classifier_branch(self.classif2[0], self.classif2[1], out2, cost1)  # classif2(out2) + cost1
         cost3 = classifier_branch(self.classif3[0], self.classif3[1], out3, cost2)
@@ -92,6 +100,8 @@ class PSMAggregator(nn.Module):
         # it writes and leaves it as a hint on the tensor: FasterSoftArgmin / SoftArgmin with exactly those parameters
         # return it instead of reading the [B, max_disp, H, W] volume again (bit-identical either way).
         vals = ops.disp_sample_values(self.max_disp, 0, 1)
+        # (one launch per level also where the chained heads hand the levels over as one stack: a single launch with batch 3 B is
+        # 0.03 ms shorter on its own and made the step 0.035 ms LONGER, docs/design/20)
         up = []
         for c in (cost3, cost2, cost1):
             if train_fn.wants_grad(self, c):   # differentiable through the disparity

@@ -218,14 +218,39 @@ def classifier_branch(unit, head, x, residual=None):
     HeadConv3d 32 -> 1.  In eval mode with no gradient wanted, exact conv3d arithmetic, split-K semantics on and a launch that
     takes the 48 x 4 row-pair tile, both layers run as ONE convolution launch whose 32-channel output never reaches memory
     (ops_head.conv3d_k3_head); otherwise the two launches."""
-    if (isinstance(unit, FusedConv3d) and isinstance(head, HeadConv3d) and torch.is_tensor(x) and x.dim() == 5
+    if _head_fuses(unit, head, x, residual):
+        wp, scale, shift = unit._prepacked()
+        return ops_head.conv3d_k3_head(x, wp, _packed_head(head), scale, shift, head.bias_value(), residual, True)
+    return head(unit(x), residual=residual)
+
+
+def _head_fuses(unit, head, x, residual=None):
+    return (isinstance(unit, FusedConv3d) and isinstance(head, HeadConv3d) and torch.is_tensor(x) and x.dim() == 5
             and unit.out_planes == 32 and head.in_channels == 32 and unit.stride == 1 and not unit.transposed and unit.has_relu
             and not train_fn.wants_grad(unit, x) and not train_fn.wants_grad(head, x, residual)
-            and ops_head.conv3d_k3_head_applicable(x)):
+            and ops_head.conv3d_k3_head_applicable(x))
+
+
+def _packed_head(head):
+    return param_state.cached(head, "_dmb_packed_head", (head.weight,), lambda: ops_head.pack_conv3d_head_weights(head.weight.detach()))
+
+
+def classifier_chain(branches, xs):
+    """The costs of a chain of classifier branches, ``cost_k = head_k(unit_k(x_k)) + cost_{k-1}`` (PSMNet.py:70-72), where EVERY
+    branch takes the fused form of ``classifier_branch``: the convolutions leave their partial sums in one workspace each and one
+    finishing pass writes all levels (ops_head.conv3d_head_chain_finish) -- the same bits as the branches one after the other.
+    ``branches``: (unit, head) pairs, ``xs``: their inputs of one shape.  Returns [N, B, 1, D, H, W], or None where a branch does
+    not take the fused form (the caller then runs ``classifier_branch`` per level)."""
+    if not 1 <= len(branches) <= 4 or any(not torch.is_tensor(x) or x.shape != xs[0].shape for x in xs):
+        return None
+    if not all(_head_fuses(unit, head, x) for (unit, head), x in zip(branches, xs)):
+        return None
+    wss = []
+    for (unit, head), x in zip(branches, xs):
         wp, scale, shift = unit._prepacked()
-        hw = param_state.cached(head, "_dmb_packed_head", (head.weight,), lambda: ops_head.pack_conv3d_head_weights(head.weight.detach()))
-        return ops_head.conv3d_k3_head(x, wp, hw, scale, shift, head.bias_value(), residual, True)
-    return head(unit(x), residual=residual)
+        wss.append(ops_head.conv3d_k3_head_partial(x, wp, _packed_head(head), scale, shift, True))
+    B, _, D, H, W = xs[0].shape
+    return ops_head.conv3d_head_chain_finish(wss, [head.bias_value() for _, head in branches], (B, D, H, W))
 
 
 class HeadDeconv3d(nn.ConvTranspose3d):

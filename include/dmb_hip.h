@@ -277,6 +277,22 @@ int dmb_conv3d_head_pack_weights_f32(const float* w_head, float* head_wpack, voi
 int dmb_conv3d_k3_head_f32(const float* x, const float* wpack, const float* scale, const float* shift,
                            const float* head_wpack, float bias, const float* residual, float* y, float* workspace,
                            int B, int Ci, int D, int H, int W, int relu, void* stream);
+/* The two halves of dmb_conv3d_k3_head_f32 as calls of their own (that entry point IS the first followed by the second with one
+ * level), for a chain of classifier tails whose costs accumulate (PSMNet.py:70-72: cost_k = classif_k(out_k) + cost_{k-1}):
+ * dmb_conv3d_k3_head_partial_f32: the convolution launch alone; it leaves the head's partial sums in `workspace` (same size,
+ *   alignment and "fully overwritten" rule as above) and writes nothing else.
+ * dmb_conv3d_head_chain_finish_f32: ONE finishing pass for nlevels (1 .. 4) such workspaces of the same B, D, H, W.
+ *   workspaces / y: HOST arrays of nlevels device pointers; bias_host: nlevels floats on the host; residual: NULL or [B, 1, D, H, W].
+ *     y[0] = (sum of workspaces[0]'s tiles in ascending tile order) + bias_host[0] (+ residual)
+ *     y[k] = ((sum of workspaces[k]'s tiles) + bias_host[k]) + y[k - 1]
+ *   -- bit for bit what nlevels calls of dmb_conv3d_k3_head_f32 with residual = the previous level's y give, without reading
+ *   any y back.  The y[k] may be the consecutive parts of one buffer; 16-byte aligned y / residual take 16-byte accesses,
+ *   4-byte aligned ones are accepted. */
+int dmb_conv3d_k3_head_partial_f32(const float* x, const float* wpack, const float* scale, const float* shift,
+                                   const float* head_wpack, float* workspace, int B, int Ci, int D, int H, int W, int relu,
+                                   void* stream);
+int dmb_conv3d_head_chain_finish_f32(int nlevels, const float* const* workspaces, const float* bias_host, const float* residual,
+                                     float* const* y, int B, int D, int H, int W, void* stream);
 
 /* ConvTranspose3d kernel 3, stride 2, padding 1, output_padding 1 (hourglass.py:52-60):
  * x: [B, Ci, D, H, W] -> y: [B, Co, 2D, 2H, Wout];  y[o] += x[i] * w[k] with o = 2i - 1 + k.  Co = 64 or any Co <= 32
