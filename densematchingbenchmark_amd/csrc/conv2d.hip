@@ -10,10 +10,12 @@
 // backbones/StereoNet.py:26-27) and stride 1 / 2 (compile time: a strided tile stages (TX - 1) * 2 + 1 + 2 * HALO input
 // columns and its B fragments walk LDS with stride 2).
 // Input and output may be channel windows of wider tensors (the 320-channel SPP concat is written in place).
+#include <array>
+#include <tuple>
 #include <type_traits>
 
 #include "bilinear_hp.h"
-#include "dmb_common.h"
+#include "conv2d_plan.h"
 
 // Workgroups per CU the kernel is built for (build-time experiment knob, build.py DMB_BUILD_DEFS): LDS budget per workgroup,
 // register cap and persistent grid follow it.
@@ -52,7 +54,7 @@ __global__ void pack_conv2d_kernel(const float* __restrict__ w, float* __restric
 // issues 64-lane memory instructions (a 3x3 layer has 3x less arithmetic per staged byte than the 3x3x3 ones), not by
 // bytes: 32->32 at 384x1248 ran 1.65 ms with dword copies / stores against 0.97 ms with neither.
 // RYO: output rows per wave, 0 = the default (4 at stride 1).  The persistent grid is two workgroups per CU and a launch of the
-// backbone is a few tile rounds deep, so the tile HEIGHT is picked per launch by rounds x rows (launch_conv2d_auto): 8 images of
+// backbone is a few tile rounds deep, so the tile HEIGHT is picked per launch by rounds x rows (conv2d_plan): 8 images of
 // 136 x 240 at 64 channels are 680 tiles of 8 rows = 1.33 rounds on 512 slots (the chip works for 2) or 1360 tiles of 4 rows
 // = 2.66 rounds (it works for 3 half-sized ones): 0.195 -> 0.16 ms for each of PSMNet's 31 layer2 convolutions.
 template <int NTT_, int KS_, int DIL_, int S_ = 1, bool V16_ = true, bool DOT_ = false, int RYO_ = 0>
@@ -521,6 +523,129 @@ __global__ __launch_bounds__(256) void bilinear_hp_kernel(const float* __restric
   y[(((size_t)b * out_ctot + out_coff + c) * Ho + yo) * Wo + xo] = hp_blend(p0[tx.i0], p0[tx.i1], p1[tx.i0], p1[tx.i1], tx.l, ty.l, mult);
 }
 
+// ---- The instantiations dmb_conv2d_f32 can run: ONE list, keyed by (row tiles, kernel size, dilation, stride, vector or scalar
+// staging, rows per wave).  A C2_TILES plan code carries the position in the list (include/dmb_hip.h numbers them); conv2d_plan finds
+// a launch's candidates by key and c2_visit is the only place where a position becomes a type.
+using C2Tiles = std::tuple<
+    // stride 1, 3x3, 32 / 64 / 128 output channels: scalar; vector with four rows per wave (64 channels only, see conv2d_plan), with two
+    C2Cfg<1, 3, 1, 1, false>, C2Cfg<1, 3, 1, 1, true, false, 2>,                           //  0  1
+    C2Cfg<2, 3, 1, 1, false>, C2Cfg<2, 3, 1, 1, true>, C2Cfg<2, 3, 1, 1, true, false, 2>,  //  2  3  4   PSMNet layer2 / StereoNet trunk widths
+    C2Cfg<4, 3, 1, 1, false>, C2Cfg<4, 3, 1, 1, true, false, 2>,                           //  5  6
+    // ... dilation 2
+    C2Cfg<1, 3, 2, 1, false>, C2Cfg<1, 3, 2, 1, true>,                                     //  7  8
+    C2Cfg<2, 3, 2, 1, false>, C2Cfg<2, 3, 2, 1, true>,                                     //  9 10
+    C2Cfg<4, 3, 2, 1, false>, C2Cfg<4, 3, 2, 1, true, false, 2>,                           // 11 12
+    // ... dilation 4 and 8, 32 output channels
+    C2Cfg<1, 3, 4, 1, false>, C2Cfg<1, 3, 4, 1, true>, C2Cfg<1, 3, 8, 1, false>, C2Cfg<1, 3, 8, 1, true>,   // 13 14 15 16
+    // stride 1, 1x1
+    C2Cfg<1, 1, 1, 1, false>, C2Cfg<1, 1, 1, 1, true>, C2Cfg<2, 1, 1, 1, false>, C2Cfg<2, 1, 1, 1, true>,   // 17 18 19 20
+    C2Cfg<4, 1, 1, 1, false>, C2Cfg<4, 1, 1, 1, true>,                                                      // 21 22
+    // stride 2: 3x3, 1x1 (32 / 64 output channels), 5x5 (32)
+    C2Cfg<1, 3, 1, 2, false>, C2Cfg<1, 3, 1, 2, true>, C2Cfg<2, 3, 1, 2, false>, C2Cfg<2, 3, 1, 2, true>,   // 23 24 25 26
+    C2Cfg<1, 1, 1, 2, false>, C2Cfg<1, 1, 1, 2, true>, C2Cfg<2, 1, 1, 2, false>, C2Cfg<2, 1, 1, 2, true>,   // 27 28 29 30
+    C2Cfg<1, 5, 1, 2, false>, C2Cfg<1, 5, 1, 2, true>                                                       // 31 32
+#ifdef DMB_DEV
+    // four rows per wave where the plan never picks them (conv2d_plan): development option 18 = 1 and scripts/kbench2d.py only
+    , C2Cfg<1, 3, 1, 1, true>, C2Cfg<4, 3, 1, 1, true>, C2Cfg<4, 3, 2, 1, true>                             // 33 34 35
+#endif
+    >;
+// the other launches of conv2d_kernel: several jobs per launch (dmb_conv2d_k3_multi_f32), the fused confidence head (C2Cfg::DOT)
+template <int NTT>
+using C2MultiCfg = C2Cfg<NTT, 3, 1, 1, true>;
+template <bool V16>
+using C2DotCfg = C2Cfg<4, 3, 1, 1, V16, true>;
+
+constexpr int C2_NTILES = (int)std::tuple_size_v<C2Tiles>;
+struct C2Tile {
+  int ntt, ks, dil, s;
+  bool v16;
+  int ry, tx, ty;
+};
+template <size_t... I>
+constexpr std::array<C2Tile, sizeof...(I)> c2_tiles(std::index_sequence<I...>) {
+  return {{{std::tuple_element_t<I, C2Tiles>::NTT, std::tuple_element_t<I, C2Tiles>::KS, std::tuple_element_t<I, C2Tiles>::DIL,
+            std::tuple_element_t<I, C2Tiles>::S, std::tuple_element_t<I, C2Tiles>::V16, std::tuple_element_t<I, C2Tiles>::RY,
+            std::tuple_element_t<I, C2Tiles>::TX, std::tuple_element_t<I, C2Tiles>::TY}...}};
+}
+constexpr auto C2_TILE = c2_tiles(std::make_index_sequence<C2_NTILES>{});
+static int c2_find(int ntt, int ks, int dil, int s, bool v16, int ry) {
+  for (int k = 0; k < C2_NTILES; ++k) {
+    const C2Tile& t = C2_TILE[k];
+    if (t.ntt == ntt && t.ks == ks && t.dil == dil && t.s == s && t.v16 == v16 && t.ry == ry) return k;
+  }
+  return -1;
+}
+template <class F, size_t... I>
+static int c2_visit(int k, F&& f, std::index_sequence<I...>) {
+  int rc = DMB_EUNSUPPORTED;
+  const bool hit = ((k == (int)I && ((rc = f(std::tuple_element_t<I, C2Tiles>{})), true)) || ...);
+  return hit ? rc : fail(DMB_EUNSUPPORTED, "conv2d: the plan names a tile this build does not hold");
+}
+// f(C2Cfg{}) for the k-th type of the list
+template <class F>
+static int c2_visit(int k, F&& f) { return c2_visit(k, f, std::make_index_sequence<C2_NTILES>{}); }
+
+// The plan of a launch: every condition that decides which kernel dmb_conv2d_f32 runs, and every refusal (conv2d_plan.h)
+int conv2d_plan(const Conv2dDesc& d, const char** why) {
+  const int B = d.B, Ci = d.Ci, Co = d.Co, H = d.H, W = d.W, ksize = d.ksize, stride = d.stride, dilation = d.dilation;
+  auto refuse = [&](int err, const char* msg) { return *why = msg, -err; };
+  const long long LIM = 0x7fffffffLL;
+  if (B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0) return refuse(DMB_EINVAL, "conv2d: bad argument");
+  if (stride != 1 && stride != 2) return refuse(DMB_EUNSUPPORTED, "conv2d: stride must be 1 or 2");
+  if (d.in_ctot < Ci || d.out_ctot < Co || d.res_ctot < Co) return refuse(DMB_EINVAL, "conv2d: channel window");
+  // (+ 8: the staging adds the chunk's first channel, < Ci rounded up to the chunk size, to per-lane offsets of which DMA_OOB =
+  // 2^31 marks "outside the image": the sum must not wrap past 2^32 back into the tensor)
+  if ((long long)d.in_ctot * H * W * 4 >= LIM || (long long)d.out_ctot * H * W * 4 >= LIM || (long long)d.res_ctot * H * W * 4 >= LIM ||
+      (long long)(Ci + 8) * H * W * 4 >= LIM)
+    return refuse(DMB_EUNSUPPORTED, "conv2d: one batch item must stay below 2 GiB");
+  const int NTT = cdiv(Co, 32), Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+  // vector path: every row of x, y and residual starts on a 16-byte boundary
+  bool v16 = W % 4 == 0 && Wo % 4 == 0 && d.x_align >= 16 && d.y_align >= 16 && d.res_align >= 16;
+  if (DMB_OPT(3)) v16 = false;   // (development option 3: dword staging / store paths only)
+
+  // ---- 1. split-K (round 6): a 3x3 layer that would leave most of the chip idle (one small image per view: backbones/PSMNet.py:8-129
+  // as dmb/apis/inference.py:191-225 calls it) takes the form of csrc/conv3d_sk.hip.  Units = 16 x 2 pixel tiles x 32-channel row tiles.
+  if (stride == 1 && ksize == 3 && (dilation == 1 || dilation == 2) && v16) {
+    const long long units = (long long)B * cdiv(H, 2) * cdiv(W, 16) * NTT;
+    bool sk = !d.single_chain && units <= C2_SK_MAX_UNITS_PER_CU * d.ncu;
+    if (DMB_OPT(26) == 1) sk = false;   // (development option 26: 1 = never, 2 = always)
+    if (DMB_OPT(26) == 2) sk = true;
+    // every row tile of a pixel tile goes to one workgroup when the A fragments fit (a pair of row tiles, up to 64 input channels)
+    const int variant = (dilation == 2 ? 2 : 0) + (NTT % 2 == 0 && Ci / 16 <= 4 ? 1 : 0);
+    if (sk && conv2d_sk_applies(variant, d)) return (C2_SPLIT_K << 8) | variant;
+  }
+
+  // ---- 2. tiles.  Height by rounds x rows (see C2Cfg) where the list has two heights for the key: cost = rounds of the persistent grid
+  // x rows per wave.  The heights share TX and TY4 = 2 TY2, so t2 <= 2 t4, hence ceil(t2 / slots) <= 2 ceil(t4 / slots) and
+  // cost2 = 2 ceil(t2 / slots) <= 4 ceil(t4 / slots) = cost4 ALWAYS: four rows can only tie.
+  // (round 6, profiles/r06_kbench2d_tile_height.log: at equal cost the two-row tiles win for 32 and 128 output channels -- one launch of
+  // 8 images: 128 -> 128 0.611 -> 0.579 ms, 320 -> 128 1.505 -> 1.409, 32 -> 32 0.194 -> 0.185 -- and tie for 64.  Under the backbone's
+  // two view streams the tile height does not matter: the other view's launch fills a launch's tail, 14.8 ms either way.)
+  // So 32 and 128 channels take two rows whatever the size -- the release list has no four-row tile for them -- and 64 channels take
+  // four on a tie.
+  const int dil = ksize == 1 && stride == 1 ? 1 : dilation;   // (a 1x1 layer has no dilation; at stride 2 only 1 is accepted, as ever)
+  const int k_def = c2_find(NTT, ksize, dil, stride, v16, stride == 1 ? 4 : 2);
+  const int k_two = stride == 1 && v16 ? c2_find(NTT, ksize, dil, 1, true, 2) : -1;
+  int k = k_def;
+  if (k_two >= 0) {
+    bool two = true;
+    if (NTT == 2) {
+      const C2Tile &c4 = C2_TILE[k_def], &c2 = C2_TILE[k_two];
+      const long long slots = (long long)C2_WPE * d.ncu;
+      const long long t4 = (long long)B * cdiv(W, c4.tx) * cdiv(H, c4.ty), t2 = (long long)B * cdiv(W, c2.tx) * cdiv(H, c2.ty);
+      two = cdiv_ll(t2, slots) * c2.ry < cdiv_ll(t4, slots) * c4.ry;
+    }
+    if (DMB_OPT(18)) two = DMB_OPT(18) == 2;   // (development option 18: 1 = always the default height, 2 = always 2 rows per wave)
+    k = two ? k_two : k_def;
+  }
+  if (k < 0)
+    return refuse(DMB_EUNSUPPORTED, "conv2d: stride 1 with kernel 1 | 3, dilation 1 | 2 (4 | 8 up to 32 output channels), output channels <= 128; "
+                                    "stride 2 with kernel 1 | 3 (<= 64 output channels) or 5 (<= 32), dilation 1");
+  if ((long long)B * cdiv(Wo, C2_TILE[k].tx) * cdiv(Ho, C2_TILE[k].ty) > LIM) return refuse(DMB_EUNSUPPORTED, "conv2d: grid too large");
+  return (C2_TILES << 8) | k;
+}
+
+// (the caller has checked that the grid fits: conv2d_plan, dmb_conf_phase_conv2d_f32)
 template <class C>
 static int launch_conv2d(const float* x, const float* wp, const float* scale, const float* shift, const float* res,
                          float* y, int B, int Ci, int Co, int H, int W, int relu, int in_ctot, int out_ctot,
@@ -528,7 +653,6 @@ static int launch_conv2d(const float* x, const float* wp, const float* scale, co
   const int Ho = (H - 1) / C::S + 1, Wo = (W - 1) / C::S + 1;
   const int ntx = cdiv(Wo, C::TX), nty = cdiv(Ho, C::TY);
   const long long ntiles = (long long)B * ntx * nty * (C::DOT ? res_ctot : 1);
-  if (ntiles > 0x7fffffffLL) return fail(DMB_EUNSUPPORTED, "conv2d: grid too large");
   const size_t lds = (size_t)C::LDS_FLOATS * sizeof(float);
   DMB_ENSURE_LDS((&conv2d_kernel<C>), (size_t)(lds));
   const long long slots = (long long)C2_WPE * num_cus();   // C2_WPE workgroups per CU, a multiple of the 8 XCDs
@@ -536,25 +660,6 @@ static int launch_conv2d(const float* x, const float* wp, const float* scale, co
   hipLaunchKernelGGL((conv2d_kernel<C>), dim3(grid), dim3(256), lds, st, x, wp, scale, shift, res, y, Ci, Co, H, W, relu,
                      in_ctot, out_ctot, res_ctot, ntx, nty, (int)ntiles, C2Jobs{});
   return launch_status("conv2d launch failed");
-}
-
-// Tile height by rounds x rows (see C2Cfg): the default 4 rows per wave, or 2 where that takes less of the chip's time.
-template <int N, int K, int DL, bool V16>
-static int launch_conv2d_auto(const float* x, const float* wp, const float* scale, const float* shift, const float* res,
-                              float* y, int B, int Ci, int Co, int H, int W, int relu, int in_ctot, int out_ctot,
-                              int res_ctot, hipStream_t st) {
-  using C4 = C2Cfg<N, K, DL, 1, V16, false, 0>;
-  using C2 = C2Cfg<N, K, DL, 1, V16, false, 2>;
-  const long long slots = (long long)C2_WPE * num_cus();
-  const long long t4 = (long long)B * cdiv(W, C4::TX) * cdiv(H, C4::TY), t2 = (long long)B * cdiv(W, C2::TX) * cdiv(H, C2::TY);
-  const long long cost4 = ((t4 + slots - 1) / slots) * C4::RY, cost2 = ((t2 + slots - 1) / slots) * C2::RY;
-  // (round 6, profiles/r06_kbench2d_tile_height.log: at equal cost the two-row tiles win for 32 and 128 output channels -- one launch of
-  // 8 images: 128 -> 128 0.611 -> 0.579 ms, 320 -> 128 1.505 -> 1.409, 32 -> 32 0.194 -> 0.185 -- and tie for 64.  Under the backbone's
-  // two view streams the tile height does not matter: the other view's launch fills a launch's tail, 14.8 ms either way.)
-  const bool two = cost2 < cost4 || (cost2 == cost4 && N != 2);
-  if ((two && !DMB_OPT(18)) || DMB_OPT(18) == 2)   // (development option 18: 1 = always the default height, 2 = always 2 rows per wave)
-    return launch_conv2d<C2>(x, wp, scale, shift, res, y, B, Ci, Co, H, W, relu, in_ctot, out_ctot, res_ctot, st);
-  return launch_conv2d<C4>(x, wp, scale, shift, res, y, B, Ci, Co, H, W, relu, in_ctot, out_ctot, res_ctot, st);
 }
 
 // Several convolutions of one layer shape in ONE launch (see C2Jobs): no affine, no residual, no ReLU, stride 1.
@@ -638,92 +743,42 @@ extern "C" int dmb_catconv_pack_weights_f32(const float* w, float* packs, int Co
   return launch_status("catconv_pack launch failed");
 }
 
+// A launch without residual: its channel total takes no part in the plan (raised to Co, which passes the window check and which the
+// 2 GiB check already covers through out_channels_total >= Co)
+static Conv2dDesc c2_desc(int B, int Ci, int Co, int H, int W, int ksize, int stride, int dilation, int in_ctot, int out_ctot, int res_ctot,
+                          bool has_res, int x_align, int y_align, int res_align, bool single_chain, int ncu) {
+  return {B, Ci, Co, H, W, ksize, stride, dilation, in_ctot, out_ctot, has_res || res_ctot >= Co ? res_ctot : Co,
+          x_align, y_align, has_res ? res_align : 16, single_chain, ncu};
+}
+
+extern "C" int dmb_conv2d_plan(int B, int Ci, int Co, int H, int W, int ksize, int stride, int dilation, int in_channels_total,
+                               int out_channels_total, int res_channels_total, int x_align, int y_align, int residual_align,
+                               int single_chain, int ncu) {
+  const char* why = "";
+  const int plan = conv2d_plan(c2_desc(B, Ci, Co, H, W, ksize, stride, dilation, in_channels_total, out_channels_total, res_channels_total,
+                                       res_channels_total != 0, x_align, y_align, residual_align, single_chain != 0, ncu > 0 ? ncu : num_cus()), &why);
+  set_last_error(why);
+  return plan;
+}
+
 extern "C" int dmb_conv2d_f32(const float* x, const float* wpack, const float* scale, const float* shift,
                               const float* residual, float* y, int B, int Ci, int Co, int H, int W, int ksize, int stride,
                               int dilation, int relu, int in_channels_total, int out_channels_total,
                               int res_channels_total, void* stream) {
-  if (!x || !wpack || !y || B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0) return fail(DMB_EINVAL, "conv2d: bad argument");
-  if (stride != 1 && stride != 2) return fail(DMB_EUNSUPPORTED, "conv2d: stride must be 1 or 2");
-  if (in_channels_total < Ci || out_channels_total < Co || (residual && res_channels_total < Co))
-    return fail(DMB_EINVAL, "conv2d: channel window");
-  // (+ 8: the staging adds the chunk's first channel, < Ci rounded up to the chunk size, to per-lane offsets of which DMA_OOB =
-  // 2^31 marks "outside the image": the sum must not wrap past 2^32 back into the tensor)
-  if ((long long)in_channels_total * H * W * 4 >= 0x7fffffffLL || (long long)out_channels_total * H * W * 4 >= 0x7fffffffLL ||
-      (long long)res_channels_total * H * W * 4 >= 0x7fffffffLL || (long long)(Ci + 8) * H * W * 4 >= 0x7fffffffLL)
-    return fail(DMB_EUNSUPPORTED, "conv2d: one batch item must stay below 2 GiB");
-  const int NTT = cdiv(Co, 32);
+  if (!x || !wpack || !y) return fail(DMB_EINVAL, "conv2d: bad argument");
+  const char* why = "";
+  const int plan = conv2d_plan(c2_desc(B, Ci, Co, H, W, ksize, stride, dilation, in_channels_total, out_channels_total, res_channels_total,
+                                       residual != nullptr, align_of(x), align_of(y), align_of(residual), (relu & DMB_CONV_SINGLE_CHAIN) != 0, num_cus()), &why);
+  if (plan < 0) return fail(-plan, why);
   hipStream_t st = (hipStream_t)stream;
-  const bool single_chain = (relu & DMB_CONV_SINGLE_CHAIN) != 0;
   relu &= 0xff;
-  // vector path: every row of x, y and residual starts on a 16-byte boundary
-  const int Wo_ = (W - 1) / stride + 1;
-  const bool v16 = W % 4 == 0 && Wo_ % 4 == 0 && !DMB_OPT(3) &&
-                   (((uintptr_t)x | (uintptr_t)y | (uintptr_t)residual) & 15) == 0;
-  // (round 6) a 3x3 layer that would leave most of the chip idle (one small image per view: backbones/PSMNet.py:8-129 as
-  // dmb/apis/inference.py:191-225 calls it) takes the split-K form of csrc/conv3d_sk.hip: units = 16 x 2 pixel tiles x 32-channel
-  // row tiles.  DMB_OPT(26) (development build): 1 = never, 2 = always.
-  if (stride == 1 && ksize == 3 && (dilation == 1 || dilation == 2) && v16) {
-    const long long units = (long long)B * cdiv(H, 2) * cdiv(W, 16) * NTT;
-    if (((!single_chain && units <= C2_SK_MAX_UNITS_PER_CU * num_cus()) && DMB_OPT(26) != 1) || DMB_OPT(26) == 2) {
-      const int rc = conv2d_sk_try(x, wpack, scale, shift, residual, y, B, Ci, Co, H, W, dilation, relu, in_channels_total,
-                                   out_channels_total, res_channels_total, st);
-      if (rc != -1) return rc;
-    }
-  }
-#define DMB_C2(N, K, DL, S)                                                                                           \
-  return v16 ? launch_conv2d<C2Cfg<N, K, DL, S, true>>(x, wpack, scale, shift, residual, y, B, Ci, Co, H, W, relu,     \
-                                                       in_channels_total, out_channels_total, res_channels_total, st)  \
-             : launch_conv2d<C2Cfg<N, K, DL, S, false>>(x, wpack, scale, shift, residual, y, B, Ci, Co, H, W, relu,    \
-                                                        in_channels_total, out_channels_total, res_channels_total, st)
-  if (stride == 1) {
-    if (ksize == 3 && dilation == 1) {
-      // the tile height follows the launch's size (launch_conv2d_auto; round 6: for every output width, not only 64 channels)
-      if (NTT == 1) {
-        if (v16) return launch_conv2d_auto<1, 3, 1, true>(x, wpack, scale, shift, residual, y, B, Ci, Co, H, W, relu, in_channels_total,
-                                                          out_channels_total, res_channels_total, st);
-        DMB_C2(1, 3, 1, 1);
-      }
-      if (NTT == 2) {   // PSMNet layer2 / StereoNet trunk widths
-        if (v16) return launch_conv2d_auto<2, 3, 1, true>(x, wpack, scale, shift, residual, y, B, Ci, Co, H, W, relu, in_channels_total,
-                                                          out_channels_total, res_channels_total, st);
-        DMB_C2(2, 3, 1, 1);
-      }
-      if (NTT == 4) {
-        if (v16) return launch_conv2d_auto<4, 3, 1, true>(x, wpack, scale, shift, residual, y, B, Ci, Co, H, W, relu, in_channels_total,
-                                                          out_channels_total, res_channels_total, st);
-        DMB_C2(4, 3, 1, 1);
-      }
-    } else if (ksize == 3 && dilation == 2) {
-      if (NTT == 1) DMB_C2(1, 3, 2, 1);
-      if (NTT == 2) DMB_C2(2, 3, 2, 1);
-      if (NTT == 4) {
-        if (v16) return launch_conv2d_auto<4, 3, 2, true>(x, wpack, scale, shift, residual, y, B, Ci, Co, H, W, relu, in_channels_total,
-                                                          out_channels_total, res_channels_total, st);
-        DMB_C2(4, 3, 2, 1);
-      }
-    } else if (ksize == 3 && dilation == 4) {
-      if (NTT == 1) DMB_C2(1, 3, 4, 1);
-    } else if (ksize == 3 && dilation == 8) {
-      if (NTT == 1) DMB_C2(1, 3, 8, 1);
-    } else if (ksize == 1) {
-      if (NTT == 1) DMB_C2(1, 1, 1, 1);
-      if (NTT == 2) DMB_C2(2, 1, 1, 1);
-      if (NTT == 4) DMB_C2(4, 1, 1, 1);
-    }
-  } else if (dilation == 1) {
-    if (ksize == 3) {
-      if (NTT == 1) DMB_C2(1, 3, 1, 2);
-      if (NTT == 2) DMB_C2(2, 3, 1, 2);
-    } else if (ksize == 1) {
-      if (NTT == 1) DMB_C2(1, 1, 1, 2);
-      if (NTT == 2) DMB_C2(2, 1, 1, 2);
-    } else if (ksize == 5) {
-      if (NTT == 1) DMB_C2(1, 5, 1, 2);
-    }
-  }
-#undef DMB_C2
-  return fail(DMB_EUNSUPPORTED, "conv2d: stride 1 with kernel 1 | 3, dilation 1 | 2 (4 | 8 up to 32 output channels), output channels <= 128; "
-                                "stride 2 with kernel 1 | 3 (<= 64 output channels) or 5 (<= 32), dilation 1");
+  if (plan >> 8 == C2_SPLIT_K)
+    return conv2d_sk_launch(plan & 0xff, x, wpack, scale, shift, residual, y, B, Ci, Co, H, W, relu, in_channels_total, out_channels_total,
+                            res_channels_total, st);
+  return c2_visit(plan & 0xff, [&](auto c) {
+    return launch_conv2d<decltype(c)>(x, wpack, scale, shift, residual, y, B, Ci, Co, H, W, relu, in_channels_total, out_channels_total,
+                                      res_channels_total, st);
+  });
 }
 
 extern "C" int dmb_conv2d_k3_multi_f32(int njobs, const float* const* x, const float* const* wpack, float* const* y, const int* W,
@@ -746,9 +801,9 @@ extern "C" int dmb_conv2d_k3_multi_f32(int njobs, const float* const* x, const f
   }
   const int NTT = cdiv(Co, 32);
   hipStream_t st = (hipStream_t)stream;
-  if (NTT == 1) return launch_conv2d_multi<C2Cfg<1, 3, 1, 1, true>>(jobs, B, Ci, Co, H, st);
-  if (NTT == 2) return launch_conv2d_multi<C2Cfg<2, 3, 1, 1, true>>(jobs, B, Ci, Co, H, st);
-  if (NTT == 4) return launch_conv2d_multi<C2Cfg<4, 3, 1, 1, true>>(jobs, B, Ci, Co, H, st);
+  if (NTT == 1) return launch_conv2d_multi<C2MultiCfg<1>>(jobs, B, Ci, Co, H, st);
+  if (NTT == 2) return launch_conv2d_multi<C2MultiCfg<2>>(jobs, B, Ci, Co, H, st);
+  if (NTT == 4) return launch_conv2d_multi<C2MultiCfg<4>>(jobs, B, Ci, Co, H, st);
   return fail(DMB_EUNSUPPORTED, "conv2d_multi: output channels <= 64 or 97 .. 128");
 }
 
@@ -760,9 +815,11 @@ extern "C" int dmb_conf_phase_conv2d_f32(const float* c, const float* wpack, con
     return fail(DMB_EUNSUPPORTED, "conf_phase_conv2d: one batch item must stay below 2 GiB");
   hipStream_t st = (hipStream_t)stream;
   const bool v16 = Wq % 4 == 0 && !DMB_OPT(3) && (((uintptr_t)c) & 15) == 0;
+  if ((long long)B * cdiv(Wq, C2DotCfg<true>::TX) * cdiv(Hq, C2DotCfg<true>::TY) * nsets > 0x7fffffffLL)   // (both tiles are 48 x 4)
+    return fail(DMB_EUNSUPPORTED, "conv2d: grid too large");
   // (`res` carries the 64 dot weights, `y` the confidence map, `res_ctot` the number of weight sets: see C2Cfg::DOT)
-  return v16 ? launch_conv2d<C2Cfg<4, 3, 1, 1, true, true>>(c, wpack, scale, shift, w2, conf, B, Ci, 128, Hq, Wq, 1, Ci, 0, nsets, st)
-             : launch_conv2d<C2Cfg<4, 3, 1, 1, false, true>>(c, wpack, scale, shift, w2, conf, B, Ci, 128, Hq, Wq, 1, Ci, 0, nsets, st);
+  return v16 ? launch_conv2d<C2DotCfg<true>>(c, wpack, scale, shift, w2, conf, B, Ci, 128, Hq, Wq, 1, Ci, 0, nsets, st)
+             : launch_conv2d<C2DotCfg<false>>(c, wpack, scale, shift, w2, conf, B, Ci, 128, Hq, Wq, 1, Ci, 0, nsets, st);
 }
 
 extern "C" int dmb_avgpool2d_f32(const float* x, float* y, int B, int C, int H, int W, int k, int in_channels_total,

@@ -21,8 +21,11 @@
 // in the last bits (and with them batch 1 from batch 4 where this form is picked) -- both are FP32 evaluations of the same
 // convolution; the tests bound them against the FP64 yardstick instead of against each other.
 //
-// Which launches take this form is a cost estimate in conv3d_plan (conv3d.hip) and deconv_plan (deconv3d_plan.h); conv3d_sk_applies
-// tells the former where the shape does not qualify.
+// Which launches take this form is a cost estimate in conv3d_plan (conv3d.hip), deconv_plan (deconv3d_plan.h) and conv2d_plan
+// (conv2d.hip); conv3d_sk_applies / conv2d_sk_applies tell the first and the last where the shape does not qualify.
+#include <tuple>
+
+#include "conv2d_plan.h"
 #include "deconv3d_plan.h"
 
 namespace dmb {
@@ -332,32 +335,35 @@ int conv3d_sk_launch(int variant, const float* x, const float* wp, const float* 
   return rc == -1 ? fail(DMB_EUNSUPPORTED, "conv3d: the plan names a split-K variant this build does not hold") : rc;
 }
 
-// The 2-D layers (dmb_conv2d_f32, kernel 3, stride 1, dilation 1 or 2) in the same form: x / y / residual are the channel windows
-// the caller has already offset, `*_ctot` the channels a batch item of each tensor holds.  relu: after the skip add (conv2d.hip).
-// -1: the shape does not qualify (every row tile of a pixel tile goes to one workgroup when the A fragments fit, else one each).
-int conv2d_sk_try(const float* x, const float* wp, const float* scale, const float* shift, const float* res, float* y, int B, int Ci,
-                  int Co, int H, int W, int dilation, int relu, int in_ctot, int out_ctot, int res_ctot, hipStream_t st) {
-  constexpr int NW = 8;
-  if (Ci % (2 * NW) != 0 || Co % 32 != 0 || Co > 128 || W % 4 != 0 || ((((uintptr_t)x) | ((uintptr_t)y) | ((uintptr_t)res)) & 15) != 0) return -1;
-  if ((long long)(Ci / NW) * H * W * 4 >= 0x7fffffffLL) return -1;
-  const int NP = Ci / (2 * NW), NTT = Co / 32;
-#define DMB_SK2(NT, NPR, DL)                                                                                        \
-  do {                                                                                                              \
-    using C = SKCfg<1, NW, NT, 1, 1, NPR, 1, DL>;                                                                   \
-    if (NP > NPR || sk_lds_bytes<C>(Ci) > 160 * 1024) return -1;                                                    \
-    return launch_sk<C>(x, wp, scale, shift, res, y, B, Ci, Co, 1, H, W, relu ? 1 : 0, st, in_ctot, out_ctot, res_ctot); \
-  } while (0)
-  // A fragments per wave = NP x 9 x NT registers: both row tiles of a pair up to 64 input channels, one above (both with 128 input
-  // channels = 144 registers: measured, spills and 30.4 against 32.4 us -- not kept)
-  if (dilation == 1) {
-    if (NTT % 2 == 0 && NP <= 4) DMB_SK2(2, 4, 1);
-    DMB_SK2(1, 8, 1);
-  } else if (dilation == 2) {
-    if (NTT % 2 == 0 && NP <= 4) DMB_SK2(2, 4, 2);
-    DMB_SK2(1, 8, 2);
-  }
-#undef DMB_SK2
-  return -1;
+// The 2-D layers (dmb_conv2d_f32, kernel 3, stride 1, dilation 1 or 2) in the same form.  Variant = (dilation 2 ? 2 : 0) + (both row
+// tiles of a pair per workgroup ? 1 : 0): A fragments per wave = channel pairs x 9 x NT registers, so both row tiles up to 64 input
+// channels (NPR 4), one up to 128 (both with 128 input channels = 144 registers: measured, spills and 30.4 against 32.4 us -- not kept)
+using SK2Tiles = std::tuple<SKCfg<1, SK_NW, 1, 1, 1, 8, 1, 1>, SKCfg<1, SK_NW, 2, 1, 1, 4, 1, 1>, SKCfg<1, SK_NW, 1, 1, 1, 8, 1, 2>,
+                            SKCfg<1, SK_NW, 2, 1, 1, 4, 1, 2>>;
+template <class F, size_t... I>
+static int sk2_visit(int variant, F&& f, std::index_sequence<I...>) {
+  int rc = -1;
+  (void)((variant == (int)I && ((rc = f(std::tuple_element_t<I, SK2Tiles>{})), true)) || ...);
+  return rc;
+}
+constexpr auto SK2_ALL = std::make_index_sequence<std::tuple_size_v<SK2Tiles>>{};
+
+bool conv2d_sk_applies(int variant, const Conv2dDesc& d) {
+  const int Ci = d.Ci, NP = Ci / (2 * SK_NW);
+  if (Ci % (2 * SK_NW) != 0 || d.Co % 32 != 0 || d.Co > 128 || d.W % 4 != 0 || d.x_align < 16 || d.y_align < 16 || d.res_align < 16) return false;
+  if ((long long)(Ci / SK_NW) * d.H * d.W * 4 >= 0x7fffffffLL) return false;   // 32-bit offsets inside a wave's channels
+  return sk2_visit(variant, [&](auto c) {
+           using C = decltype(c);
+           return (C::DIL != d.dilation || d.Co / 32 % C::NT != 0 || NP > C::NPR || sk_lds_bytes<C>(Ci) > 160 * 1024) ? -1 : 0;
+         }, SK2_ALL) == 0;
+}
+
+int conv2d_sk_launch(int variant, const float* x, const float* wp, const float* scale, const float* shift, const float* res, float* y,
+                     int B, int Ci, int Co, int H, int W, int relu, int in_ctot, int out_ctot, int res_ctot, hipStream_t st) {
+  const int rc = sk2_visit(variant, [&](auto c) {
+    return launch_sk<decltype(c)>(x, wp, scale, shift, res, y, B, Ci, Co, 1, H, W, relu ? 1 : 0, st, in_ctot, out_ctot, res_ctot);
+  }, SK2_ALL);
+  return rc == -1 ? fail(DMB_EUNSUPPORTED, "conv2d: the plan names a split-K variant this build does not hold") : rc;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

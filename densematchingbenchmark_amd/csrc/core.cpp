@@ -30,7 +30,7 @@ int num_cus() {
 //    6  diagnostic bits of the conv3d kernels (no stores, no staging)   10  stride 2: 1 = four-wave workgroups, 2 = dword epilogue
 //   13  = 1: box tiles instead of linear runs (stride-1, 64 ch)         14  start-up stagger unit of the stride-1 kernels
 //   16  zy item order: tiles per class run (0 = default)                17  extra KB of LDS per stride-1 workgroup (occupancy)
-//   18  = 1: default tile height for the 64-channel conv2d layers       19  stride-1 tile override (see dmb_conv3d_k3_f32)
+//   18  = 1 / 2: four / two rows per wave in conv2d_plan                19  stride-1 tile override (see dmb_conv3d_k3_f32)
 //   20  = 1: zy items from ONE counter instead of one per XCD           22  up-sampling: 1 = row form, 2 = flat form
 //   23  split-K conv3d: 1 = never, k >= 2 = force variant k - 1          24  32 -> 1 head: 1 = never the split-channel form, 2 = always
 //   25  split-K transposed conv: 1 = never, 2 = force                   26  split-K 3x3 conv2d: 1 = never, 2 = always

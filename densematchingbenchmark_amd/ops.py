@@ -1562,6 +1562,28 @@ def conv2d(x, wpack, Co, ksize, stride=1, dilation=1, scale=None, shift=None, re
     return out
 
 
+CONV2D_PLAN_SPLIT_K, CONV2D_PLAN_TILES = 1, 2   # dmb_conv2d_plan: the form, bits 8.. of a plan code
+
+
+def conv2d_plan(x, Co, ksize, stride=1, dilation=1, residual=None, in_window=None, out=None, out_ch_offset=0, res_ch_offset=0, ncu=0):
+    """What ``conv2d(x, wpack, Co, ksize, ...)`` with the same operands would run under the current small-launch policy
+    (``set_split_k``): the plan code (form << 8) | index of dmb_conv2d_plan (include/dmb_hip.h), or minus the DMB_E* code of a
+    refusal.  ``x`` may be a shape (B, Cx, H, W): every tensor then counts as 16-byte aligned, as does a fresh output (``out`` None);
+    the alignments passed on are those of the WINDOW pointers.  ``ncu``: compute units to plan for, 0 = the current device's."""
+    is_shape = isinstance(x, (tuple, list))
+    B, Cx, H, W = (int(v) for v in (x if is_shape else x.shape))
+    coff, Ci = in_window if in_window is not None else (0, Cx)
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+
+    def align(t, ch_offset, hw):
+        p = (0 if t is None else t.data_ptr()) + 4 * ch_offset * hw
+        return min(p & -p or 16, 16)
+    return _lib.load().dmb_conv2d_plan(B, int(Ci), int(Co), H, W, int(ksize), int(stride), int(dilation), Cx,
+                                       int(Co) if out is None else out.shape[1], 0 if residual is None else residual.shape[1],
+                                       align(None if is_shape else x, coff, H * W), align(out, out_ch_offset if out is not None else 0, Ho * Wo),
+                                       align(residual, res_ch_offset if residual is not None else 0, Ho * Wo), 0 if _split_k else 1, int(ncu))
+
+
 def conv2d_k3_multi(jobs, Co):
     """``jobs``: list of (x [B, Ci, H, W_q], wpack, out [B, Ctot_q, H, W_q], out_ch_offset): independent 3x3 stride-1 convolutions
     of one layer shape in ONE launch (csrc/conv2d.hip, MULTI); no affine / residual / ReLU."""

@@ -44,13 +44,13 @@ extern "C" {
 
 #define DMB_MAX_DISP_SAMPLES 256 /* upper bound on the number of disparity samples D */
 
-/* ABI version: bumped whenever a signature below changes (10: dmb_conv3d_k3_plan added; 9: dmb_deconv3d_k3s2_plan added; 8: dmb_bn_train_fwd_f32, dmb_catconv_pack_weights_f32, dmb_conv3d_pack_weights_multi_f32, dmb_cat_first_wgrad_maps_f32, dmb_conv3d_k3_bnstats_f32 and dmb_bn_train_act_f32 added, dmb_bn_act_bwd_f32 takes the gradient its
+/* ABI version: bumped whenever a signature below changes (11: dmb_conv2d_plan added; 10: dmb_conv3d_k3_plan added; 9: dmb_deconv3d_k3s2_plan added; 8: dmb_bn_train_fwd_f32, dmb_catconv_pack_weights_f32, dmb_conv3d_pack_weights_multi_f32, dmb_cat_first_wgrad_maps_f32, dmb_conv3d_k3_bnstats_f32 and dmb_bn_train_act_f32 added, dmb_bn_act_bwd_f32 takes the gradient its
  * skip operand already holds (`dres_acc`); 7: DMB_CONV_SINGLE_CHAIN in the `relu` argument of the convolution
  * entry points, `flags` argument of dmb_conv3d_k3_c1_f32; 6: dmb_stereo_pad_normalize_f32 / _u8 added; 5: dmb_fast_fms_bwd_f32 takes a mode, the forward's norm and an
  * optional gradient buffer for per-pixel samples; 4: workspace argument of dmb_deconv3d_k3s2_f32, the merged-heads entry
  * points of version 3 removed).  The define is the one place the number is written: dmb_abi_version() returns it and the Python
  * binding reads it from this file. */
-#define DMB_ABI_VERSION 10
+#define DMB_ABI_VERSION 11
 int dmb_abi_version(void);
 /* Static string describing the last DMB_E* code returned on this thread ("" if none). */
 const char* dmb_last_error(void);
@@ -492,6 +492,31 @@ int dmb_conv2d_pack_weights_f32(const float* w, float* wpack, int Co, int Ci, in
 int dmb_conv2d_f32(const float* x, const float* wpack, const float* scale, const float* shift, const float* residual,
                    float* y, int B, int Ci, int Co, int H, int W, int ksize, int stride, int dilation, int relu,
                    int in_channels_total, int out_channels_total, int res_channels_total, void* stream);
+/* What dmb_conv2d_f32 would run for a launch, without launching anything or touching a device: a pure function of its arguments, in
+ * the conventions of dmb_conv3d_k3_plan.  The three pointers enter as the alignment in bytes of the WINDOW pointers the launch would
+ * be given (16 for a NULL residual); res_channels_total: 0 for a launch without residual.  Returns
+ *   (form << 8) | index  with form 1 = split-K over the eight waves of a workgroup (csrc/conv3d_sk.hip; 3x3, stride 1, dilation 1 | 2,
+ *                          16-byte rows, Ci % 16 == 0 and Ci <= 128, Co % 32 == 0, at most 5 units of 16 x 2 pixels x 32 channels per
+ *                          compute unit, never under single_chain): index = (dilation 2 ? 2 : 0) + (both 32-channel row tiles of a pair
+ *                          in one workgroup: Co % 64 == 0 and Ci <= 64 ? 1 : 0): 0x100 .. 0x103;
+ *                        form 2 = persistent tiles of 48 columns x (rows per wave x 4 / 2 / 1 waves for Co <= 32 / 64 / 128) rows; rows
+ *                          per wave: 4 at stride 1, 2 at stride 2, "two-row": 2 at stride 1.  Of each pair of indices below the first =
+ *                          "scalar", dword staging and stores (any W, 4-byte aligned operands), the second = 16-byte rows (W and Wo
+ *                          multiples of 4, 16-byte aligned x / y / residual windows):
+ *                            stride 1, 3x3:       0 / 1 = Co <= 32: scalar / two-row;  2 / 3 / 4 = Co <= 64: scalar / four rows per wave /
+ *                                                 two-row, by rounds of the grid x rows, four on a tie;  5 / 6 = Co <= 128: scalar / two-row
+ *                            ... dilation 2:      7 / 8 = Co <= 32,  9 / 10 = Co <= 64,  11 / 12 = Co <= 128: scalar / two-row
+ *                            ... dilation 4, 8:   13 / 14,  15 / 16 (Co <= 32)
+ *                            stride 1, 1x1:       17 / 18 = Co <= 32,  19 / 20 = Co <= 64,  21 / 22 = Co <= 128
+ *                            stride 2, 3x3:       23 / 24 = Co <= 32,  25 / 26 = Co <= 64
+ *                            stride 2, 1x1:       27 / 28 = Co <= 32,  29 / 30 = Co <= 64
+ *                            stride 2, 5x5:       31 / 32 (Co <= 32)
+ *                          (33 .. 35, development build only: four rows per wave for indices 1, 6 and 12, which no launch is planned)
+ *   or -DMB_EINVAL / -DMB_EUNSUPPORTED where the launch would be refused with that code (dmb_last_error() then names the reason).
+ * Form 2 is ONE k-ordered fma chain per output, the same bits whatever the tile, vector or scalar. */
+int dmb_conv2d_plan(int B, int Ci, int Co, int H, int W, int ksize, int stride, int dilation, int in_channels_total,
+                    int out_channels_total, int res_channels_total, int x_align, int y_align, int residual_align, int single_chain,
+                    int ncu);
 
 /* njobs (<= 6) independent 3x3 stride-1 convolutions of ONE layer shape (B, Ci -> Co, H) in one launch: job q convolves
  * x[q] [B, Ci, H, W[q]] with wpack[q] into y[q] (a channel window of a tensor with out_channels_total[q] channels); no affine,
