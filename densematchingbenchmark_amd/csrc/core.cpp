@@ -36,7 +36,8 @@ int num_cus() {
 //   25  split-K transposed conv: 1 = never, 2 = force                   26  split-K 3x3 conv2d: 1 = never, 2 = always
 //   27  stride-2 weight gradient: 1 = 2 x 12 tile, 2 = 4 x 8 tile       29  zy tile: 1 = never 32 / 64 real columns, 2 / 3 = force them
 // (7, 8, 9, 12, 21 and 28 belonged to decided experiments of the transposed convolution and are gone: scripts/README.md has the
-// findings; csrc/deconv3d_plan.h is where 3, 4, 25 and 29 act on that family.)
+// findings; csrc/deconv3d_plan.h is where 3, 4, 25 and 29 act on that family; 5 and 27 act on the weight gradients in wgrad_plan,
+// csrc/wgrad.hip, and nowhere else there.)
 namespace dmb {
 int g_dev_opts[32] = {0};
 }

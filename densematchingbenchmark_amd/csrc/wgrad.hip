@@ -16,7 +16,10 @@
 //     kernel adds the slots in a fixed order -- no atomics, bit-reproducible.
 //
 // Reference semantics: autograd of nn.Conv3d in dmb/modeling/stereo/layers/basic_layers.py:68-83,160-177.
-#include "dmb_common.h"
+#include <tuple>
+#include <utility>
+
+#include "wgrad_plan.h"
 
 namespace dmb {
 
@@ -205,7 +208,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_wgrad_s1_kernel(const float* __
 // instruction moves 64 units whatever the plane size.
 // ------------------------------------------------------------------------------------------------------------------
 // (round 6) The tile is a parameter: 2 x 12 (84 MFMAs per wave between two barriers) or 4 x 8 (112; and 64-column rows -- the
-// training crops -- tile exactly where 12-column tiles compute 72); dmb_conv3d_k3s2_wgrad_f32 picks per launch.
+// training crops -- tile exactly where 12-column tiles compute 72); wgrad_plan picks per launch.
 template <int TY_, int TX_>
 struct Wg2Cfg {
   static constexpr int TY = TY_, TX = TX_, ROWS = 2 * TY + 1, XOFF = 3;
@@ -515,7 +518,7 @@ __global__ __launch_bounds__(256) void conv3d_c1_wgrad_reduce_kernel(const float
 // its four waves a quarter of the slots each (eight interleaved partial sums per thread: independent loads), combined through LDS
 // as (q0 + q1) + (q2 + q3).  (Rounds 1-5: one thread per element walked all 256 slots -- 32 dependent rounds of 8 loads, 9.2 us for
 // 28 MB, 25 times per training step; more threads per element, not more bytes, is what it lacked.)
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int Co, int Ci, int nslots, int transposed) {
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int Co, int Ci, int nslots) {
   __shared__ double sm[4][64];
   const int ncib = cdiv(Ci, 32);
   const int e = threadIdx.x & 63, q = threadIdx.x >> 6;
@@ -541,160 +544,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
   __syncthreads();
   if (q != 0 || co >= Co || ci >= Ci) return;
   const double s = (sm[0][e] + sm[1][e]) + (sm[2][e] + sm[3][e]);
-  if (transposed)
-    dw[((size_t)ci * Co + co) * 27 + t] = (float)s;
-  else
-    dw[((size_t)co * Ci + ci) * 27 + t] = (float)s;
-}
-
-static int wgrad_slots() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
-}
-
-}  // namespace dmb
-
-using namespace dmb;
-
-// slots per (32 x 32) channel block: the CUs are shared between the blocks of one launch
-static int wgrad_slots_per_block(int Co, int Ci) {
-  const int nblk = cdiv(Co, 32) * cdiv(Ci, 32);
-  const int s = wgrad_slots() / nblk;
-  return s < 1 ? 1 : s;
-}
-
-extern "C" long long dmb_conv3d_wgrad_workspace_floats(int Co, int Ci) {
-  if (Co <= 0 || Ci <= 0) return 0;
-  return (long long)cdiv(Co, 32) * cdiv(Ci, 32) * wgrad_slots_per_block(Co, Ci) * 27 * 1024;
-}
-
-extern "C" int dmb_conv3d_k3_wgrad_f32(const float* x, const float* dc, float* dw, float* workspace, int B, int Ci, int Co,
-                                       int D, int H, int W, void* stream) {
-  if (!x || !dc || !dw || !workspace || B <= 0 || Ci <= 0 || Co <= 0 || D <= 0 || H <= 0 || W <= 0)
-    return fail(DMB_EINVAL, "conv3d_wgrad: bad argument");
-  if ((long long)32 * D * H * W * 4 >= 0x7fffffffLL) return fail(DMB_EUNSUPPORTED, "conv3d_wgrad: 32 channels of one batch item must stay below 2 GiB");
-  hipStream_t st = (hipStream_t)stream;
-  if (Co == 1) {   // classifier heads: the single-output-channel form (M = channels, N = taps, K = voxels on the matrix cores)
-    const int ntx = cdiv(W, C1M_XT), nty = cdiv(H, C1M_ROWS);
-    const long long nt = (long long)B * D * ntx * nty;
-    if (nt > 0x7fffffffLL) return fail(DMB_EUNSUPPORTED, "conv3d_wgrad (1 channel): too many tiles");
-    // persistent grid: four workgroups per CU, bounded by the tiles and by the caller's workspace ([workgroup][Ci][27] partials)
-    long long g = 4LL * wgrad_slots();
-    const long long cap = dmb_conv3d_wgrad_workspace_floats(Co, Ci) / ((long long)Ci * 27);
-    if (g > nt) g = nt;
-    if (g > cap) g = cap;
-    if (g < 1) g = 1;
-    hipLaunchKernelGGL(conv3d_c1_wgrad_kernel, dim3((unsigned)g, cdiv(Ci, 32)), dim3(256), 0, st, x, dc, workspace, B, Ci, D, H, W, ntx, nty, (int)nt);
-    hipLaunchKernelGGL(conv3d_c1_wgrad_reduce_kernel, dim3(cdiv(Ci * 27, 4)), dim3(256), 0, st, workspace, dw, Ci, (int)g);
-    return launch_status("conv3d_wgrad (1 channel) launch failed");
-  }
-  const int nblk = cdiv(Co, 32) * cdiv(Ci, 32);
-  // 24- or 32-column tiles: whichever covers W with fewer computed columns (W = 128 of the training crops: 128 against 144)
-  const bool wide = cdiv(W, 32) * 32 < cdiv(W, 24) * 24;
-  const int TX = wide ? 32 : 24;
-  const int ntx = cdiv(W, TX), nty = cdiv(H, 4);
-  // z segments: the split that minimises rounds x (planes per item + prologue); a round = one item on every slot
-  const int nslots = wgrad_slots_per_block(Co, Ci);
-  int zseg = D;
-  {
-    double best = 1e30;
-    for (int nz = 1; nz <= D; ++nz) {
-      const int zs = cdiv(D, nz);
-      if (zs < 4 && nz > 1) break;
-      const double cost = (double)cdiv_ll((long long)B * ntx * nty * cdiv(D, zs), nslots) * (zs + 0.5);
-      if (cost < best - 1e-9) {
-        best = cost;
-        zseg = zs;
-      }
-    }
-  }
-  if (DMB_OPT(5) > 0) zseg = cdiv(D, DMB_OPT(5));   // development knob: number of z segments
-  const int nzs = cdiv(D, zseg);
-  const bool v16 = W % 4 == 0 && (((uintptr_t)x | (uintptr_t)dc) & 15) == 0;
-  DMB_ENSURE_LDS((&conv3d_wgrad_s1_kernel<true, 24>), (size_t)(WgCfg<24>::LDS_FLOATS * 4));
-  DMB_ENSURE_LDS((&conv3d_wgrad_s1_kernel<true, 32>), (size_t)(WgCfg<32>::LDS_FLOATS * 4));
-  DMB_ENSURE_LDS((&conv3d_wgrad_s1_kernel<false, 24>), (size_t)(WgCfg<24>::LDS_FLOATS * 4));
-  const long long items3 = (long long)B * ntx * nty * nzs;
-  const int nused = (int)(items3 < nslots ? items3 : nslots);   // small layers: no idle slots to write and add zeros for
-  const dim3 grid((unsigned)nused, (unsigned)nblk);
-  if (v16 && wide)
-    hipLaunchKernelGGL((conv3d_wgrad_s1_kernel<true, 32>), grid, dim3(256), WgCfg<32>::LDS_FLOATS * 4, st, x, dc, workspace, B, Ci, Co, D, H, W, ntx, nty, nzs, zseg);
-  else if (v16)
-    hipLaunchKernelGGL((conv3d_wgrad_s1_kernel<true, 24>), grid, dim3(256), WgCfg<24>::LDS_FLOATS * 4, st, x, dc, workspace, B, Ci, Co, D, H, W, ntx, nty, nzs, zseg);
-  else
-    hipLaunchKernelGGL((conv3d_wgrad_s1_kernel<false, 24>), grid, dim3(256), WgCfg<24>::LDS_FLOATS * 4, st, x, dc, workspace, B, Ci, Co, D, H, W, cdiv(W, 24), nty, nzs, zseg);
-  int rc = launch_status("conv3d_wgrad launch failed");
-  if (rc != DMB_OK) return rc;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(nblk * 27 * 16), dim3(256), 0, st, workspace, dw, Co, Ci, nused, 0);
-  return launch_status("conv3d_wgrad reduce launch failed");
-}
-
-constexpr double WG2_EFF_4x8 = 1.1;   // rate of the 4 x 8 tile relative to 2 x 12 on shapes both tile exactly (calibrated below)
-
-extern "C" int dmb_conv3d_k3s2_wgrad_f32(const float* small, const float* big, float* dw, float* workspace, int B, int Cs, int Cb,
-                                         int Ds, int Hs, int Ws, int Db, int Hb, int Wb, void* stream) {
-  if (!small || !big || !dw || !workspace || B <= 0 || Cs <= 0 || Cb <= 0 || Ds <= 0 || Hs <= 0 || Ws <= 0)
-    return fail(DMB_EINVAL, "conv3d_s2_wgrad: bad argument");
-  if ((Db != 2 * Ds && Db != 2 * Ds - 1) || (Hb != 2 * Hs && Hb != 2 * Hs - 1) || (Wb != 2 * Ws && Wb != 2 * Ws - 1))
-    return fail(DMB_EINVAL, "conv3d_s2_wgrad: the big tensor must be 2n or 2n - 1 per axis");
-  if ((long long)32 * Db * Hb * Wb * 4 >= 0x7fffffffLL) return fail(DMB_EUNSUPPORTED, "conv3d_s2_wgrad: 32 channels of one batch item must stay below 2 GiB");
-  const bool v16 = Ws % 4 == 0 && Wb % 4 == 0 && (((uintptr_t)small | (uintptr_t)big) & 15) == 0;
-  hipStream_t st = (hipStream_t)stream;
-  const int nblk = cdiv(Cs, 32) * cdiv(Cb, 32);
-  const int nslots = wgrad_slots_per_block(Cs, Cb);
-  // z segments and the launch's cost for a tile shape: rounds of items on the slots x (planes per item + prologue) x the tile's
-  // k-steps, over what the tile reaches between its barriers (4 x 8: 112 MFMAs per wave and barrier against 84; measured at the
-  // training crop, profiles/r06_wgrad_s2_tiles.log)
-  auto plan = [&](int TY, int TX, double eff, int& zseg_out) {
-    const int ntx_ = cdiv(Ws, TX), nty_ = cdiv(Hs, TY);
-    double best = 1e30;
-    int zseg_ = Ds;
-    for (int nz = 1; nz <= Ds; ++nz) {
-      const int zs = cdiv(Ds, nz);
-      if (zs < 4 && nz > 1) break;
-      const double cost = (double)cdiv_ll((long long)B * ntx_ * nty_ * cdiv(Ds, zs), nslots) * (zs + 1.0);
-      if (cost < best - 1e-9) {
-        best = cost;
-        zseg_ = zs;
-      }
-    }
-    zseg_out = zseg_;
-    return best * (TY * TX) / eff;
-  };
-  int zseg_a, zseg_b;
-  const double cost_a = plan(2, 12, 1.0, zseg_a), cost_b = plan(4, 8, WG2_EFF_4x8, zseg_b);
-  bool wide = cost_b < cost_a;            // the 4 x 8 tile
-  if (DMB_OPT(27) == 1) wide = false;     // (development build: force a tile)
-  if (DMB_OPT(27) == 2) wide = true;
-  const int zseg = wide ? zseg_b : zseg_a;
-  const int ntx = cdiv(Ws, wide ? 8 : 12), nty = cdiv(Hs, wide ? 4 : 2);
-  const int nzs = cdiv(Ds, zseg);
-  const long long items2 = (long long)B * ntx * nty * nzs;
-  const int nused = (int)(items2 < nslots ? items2 : nslots);
-#define DMB_WG2(CFG, V)                                                                                                                  \
-  do {                                                                                                                                  \
-    DMB_ENSURE_LDS((&conv3d_wgrad_s2_kernel<CFG, V>), (size_t)(CFG::LDS_FLOATS * 4));                                                    \
-    hipLaunchKernelGGL((conv3d_wgrad_s2_kernel<CFG, V>), dim3((unsigned)nused, (unsigned)nblk), dim3(256), CFG::LDS_FLOATS * 4, st, small, \
-                       big, workspace, B, Cs, Cb, Ds, Hs, Ws, Db, Hb, Wb, ntx, nty, nzs, zseg);                                         \
-  } while (0)
-  typedef Wg2Cfg<2, 12> WgA;
-  typedef Wg2Cfg<4, 8> WgB;
-  if (wide) {
-    if (v16) DMB_WG2(WgB, true); else DMB_WG2(WgB, false);
-  } else {
-    if (v16) DMB_WG2(WgA, true); else DMB_WG2(WgA, false);
-  }
-#undef DMB_WG2
-  int rc = launch_status("conv3d_s2_wgrad launch failed");
-  if (rc != DMB_OK) return rc;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(nblk * 27 * 16), dim3(256), 0, st, workspace, dw, Cs, Cb, nused, 0);
-  return launch_status("conv3d_s2_wgrad reduce launch failed");
+  dw[((size_t)co * Ci + ci) * 27 + t] = (float)s;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -705,8 +555,6 @@ extern "C" int dmb_conv3d_k3s2_wgrad_f32(const float* small, const float* big, f
 // dc rows are double buffered; the four waves split the strip's columns (16 each) and each holds all nine taps (144
 // accumulator registers); their partial results are added through LDS at the end, the slots' by the reduction kernel.
 // ------------------------------------------------------------------------------------------------------------------
-namespace dmb {
-
 template <int KS_, int DIL_>
 struct Wg2dCfg {
   static constexpr int KS = KS_, DIL = DIL_, NTAP = KS * KS;
@@ -880,61 +728,213 @@ __global__ void conv2d_wgrad_reduce_kernel(const float* __restrict__ ws, float* 
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The instantiations a launch can run: ONE list per form.  Bits 0-7 of a plan code are the position in the form's list
+// (include/dmb_hip.h numbers them); wgrad_plan names a position and wg_visit is the only place where one becomes a type.
+// ------------------------------------------------------------------------------------------------------------------
+template <bool V16_, int TX_>
+struct WgS1Form {
+  typedef WgCfg<TX_> C;
+  static constexpr bool V16 = V16_;   // 16-byte staging, else dword copies
+};
+template <class C_, bool V16_>
+struct WgS2Form {
+  typedef C_ C;
+  static constexpr bool V16 = V16_;
+};
+using WgS1Forms = std::tuple<WgS1Form<true, 24>, WgS1Form<true, 32>, WgS1Form<false, 24>>;
+using WgS2Forms = std::tuple<WgS2Form<Wg2Cfg<2, 12>, true>, WgS2Form<Wg2Cfg<2, 12>, false>, WgS2Form<Wg2Cfg<4, 8>, true>, WgS2Form<Wg2Cfg<4, 8>, false>>;
+using Wg2dForms = std::tuple<Wg2dCfg<3, 1>, Wg2dCfg<3, 2>, Wg2dCfg<3, 4>, Wg2dCfg<3, 8>, Wg2dCfg<1, 1>>;
+
+template <class L, class F, size_t... I>
+static int wg_visit(int k, F&& f, std::index_sequence<I...>) {
+  int rc = DMB_EUNSUPPORTED;
+  const bool hit = ((k == (int)I && ((rc = f(std::tuple_element_t<I, L>{})), true)) || ...);
+  return hit ? rc : fail(DMB_EUNSUPPORTED, "wgrad: the plan names an instantiation this build does not hold");
+}
+// f(Form{}) for the type a plan code names in the list L of its form
+template <class L, class F>
+static int wg_visit(int code, F&& f) { return wg_visit<L>(code & 0xff, f, std::make_index_sequence<std::tuple_size_v<L>>{}); }
+
+// The planned instantiation on the planned grid, its LDS cap raised first (*seen: one static per instantiation, see ensure_dynamic_lds)
+template <class... P, class... A>
+static int wg_launch(void (*kernel)(P...), int lds_bytes, unsigned long long* seen, const WgradPlan& p, hipStream_t st, const char* what, A... args) {
+  const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (size_t)lds_bytes, seen);
+  if (rc != DMB_OK) return rc;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)p.slots, (unsigned)p.blocks), dim3(256), lds_bytes, st, args...);
+  return launch_status(what);
+}
+
+// floats of workspace: one partial result [ntap][32][32] per slot and channel block
+static long long wgrad_ws_floats(int Co, int Ci, int per_cu, int ntap, int ncu) {
+  return (long long)cdiv(Co, 32) * cdiv(Ci, 32) * wgrad_slots_per_block(Co, Ci, per_cu, ncu) * ntap * 1024;
+}
+
+// The plan of a launch: every refusal and every choice of the three entry points (wgrad_plan.h)
+int wgrad_plan(const WgradDesc& d, WgradPlan* p, const char** why) {
+  const int B = d.B, Co = d.Co, Ci = d.Ci, D = d.D, H = d.H, W = d.W, ncu = d.ncu;
+  auto refuse = [&](int err, const char* msg) { return *why = msg, err; };
+  // segments of `seg` along an axis of `extent`; no more slots than items (small layers: no idle slots to write and add zeros for)
+  auto planned = [&](int form, int index, int ntx, int nty, int extent, int seg, long long items_per_segment_count, int nslots) {
+    const int nseg = cdiv(extent, seg);
+    const long long items = items_per_segment_count * nseg;
+    *p = {(form << 8) | index, ntx, nty, seg, nseg, (int)(items < nslots ? items : nslots), cdiv(Co, 32) * cdiv(Ci, 32)};
+    return DMB_OK;
+  };
+  const bool aligned = d.align >= 16;
+  const long long LIM = 0x7fffffffLL;   // 32-bit buffer offsets
+
+  if (d.kind == DMB_WGRAD_S1) {
+    if (B <= 0 || Ci <= 0 || Co <= 0 || D <= 0 || H <= 0 || W <= 0) return refuse(DMB_EINVAL, "conv3d_wgrad: bad argument");
+    if ((long long)32 * D * H * W * 4 >= LIM) return refuse(DMB_EUNSUPPORTED, "conv3d_wgrad: 32 channels of one batch item must stay below 2 GiB");
+    if (Co == 1) {   // classifier heads: the single-output-channel form (M = channels, N = taps, K = voxels on the matrix cores)
+      const int ntx = cdiv(W, C1M_XT), nty = cdiv(H, C1M_ROWS);
+      const long long nt = (long long)B * D * ntx * nty;
+      if (nt > LIM) return refuse(DMB_EUNSUPPORTED, "conv3d_wgrad (1 channel): too many tiles");
+      // persistent grid: four workgroups per CU, bounded by the tiles and by the caller's workspace ([workgroup][Ci][27] partials)
+      long long g = 4LL * ncu;
+      const long long cap = wgrad_ws_floats(Co, Ci, 1, 27, ncu) / ((long long)Ci * 27);
+      if (g > nt) g = nt;
+      if (g > cap) g = cap;
+      if (g < 1) g = 1;
+      *p = {WGRAD_C1 << 8, ntx, nty, 1, D, (int)g, cdiv(Ci, 32)};
+      return DMB_OK;
+    }
+    // 24- or 32-column tiles: whichever covers W with fewer computed columns (W = 128 of the training crops: 128 against 144)
+    const bool wide = cdiv(W, 32) * 32 < cdiv(W, 24) * 24;
+    const bool v16 = W % 4 == 0 && aligned;
+    const int nty = cdiv(H, WgCfg<24>::TY);
+    // z segments.  Rows that cannot take 16-byte copies run the 24-column dword form on the segments and slots of their width
+    // class's tile (as ever: the split decides the order of the sums, so it stays).
+    const long long per_seg = (long long)B * cdiv(W, wide ? 32 : 24) * nty;
+    const int nslots = wgrad_slots_per_block(Co, Ci, 1, ncu);
+    int zseg = segment_search(D, per_seg, nslots, WG_SEG_S1);
+    if (DMB_OPT(5) > 0) zseg = cdiv(D, DMB_OPT(5));   // (development option 5: number of z segments)
+    return planned(WGRAD_S1, v16 ? (wide ? 1 : 0) : 2, cdiv(W, v16 && wide ? 32 : 24), nty, D, zseg, per_seg, nslots);
+  }
+
+  if (d.kind == DMB_WGRAD_S2) {   // Co / D, H, W: the small operand's; Ci / Db, Hb, Wb: the big one's
+    const int Db = d.Db, Hb = d.Hb, Wb = d.Wb;
+    if (B <= 0 || Co <= 0 || Ci <= 0 || D <= 0 || H <= 0 || W <= 0) return refuse(DMB_EINVAL, "conv3d_s2_wgrad: bad argument");
+    if ((Db != 2 * D && Db != 2 * D - 1) || (Hb != 2 * H && Hb != 2 * H - 1) || (Wb != 2 * W && Wb != 2 * W - 1))
+      return refuse(DMB_EINVAL, "conv3d_s2_wgrad: the big tensor must be 2n or 2n - 1 per axis");
+    if ((long long)32 * Db * Hb * Wb * 4 >= LIM) return refuse(DMB_EUNSUPPORTED, "conv3d_s2_wgrad: 32 channels of one batch item must stay below 2 GiB");
+    const bool v16 = W % 4 == 0 && Wb % 4 == 0 && aligned;
+    const int nslots = wgrad_slots_per_block(Co, Ci, 1, ncu);
+    // z segments and the launch's cost for a tile shape: rounds of items on the slots x (planes per item + prologue) x the tile's
+    // k-steps, over what the tile reaches between its barriers (4 x 8: 112 MFMAs per wave and barrier against 84; measured at the
+    // training crop, profiles/r06_wgrad_s2_tiles.log)
+    struct { int ty, tx; double eff; int zseg; double cost; } t[2] = {{2, 12, 1.0, 0, 0}, {4, 8, WG2_EFF_4x8, 0, 0}};
+    for (auto& c : t) {
+      c.zseg = segment_search(D, (long long)B * cdiv(W, c.tx) * cdiv(H, c.ty), nslots, WG_SEG_S2, &c.cost);
+      c.cost = c.cost * (c.ty * c.tx) / c.eff;
+    }
+    int wide = t[1].cost < t[0].cost;     // the 4 x 8 tile
+    if (DMB_OPT(27) == 1) wide = 0;       // (development option 27: 1 = always 2 x 12, 2 = always 4 x 8)
+    if (DMB_OPT(27) == 2) wide = 1;
+    const auto& c = t[wide];
+    return planned(WGRAD_S2, 2 * wide + (v16 ? 0 : 1), cdiv(W, c.tx), cdiv(H, c.ty), D, c.zseg, (long long)B * cdiv(W, c.tx) * cdiv(H, c.ty), nslots);
+  }
+
+  if (d.kind == DMB_WGRAD_2D) {
+    if (B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0) return refuse(DMB_EINVAL, "conv2d_wgrad: bad argument");
+    if ((long long)32 * H * W * 4 >= LIM) return refuse(DMB_EUNSUPPORTED, "conv2d_wgrad: 32 channels of one image must stay below 2 GiB");
+    if (W % 4 != 0 || !aligned) return refuse(DMB_EUNSUPPORTED, "conv2d_wgrad: the width must be a multiple of 4 and the tensors 16-byte aligned");
+    const int dil = d.ksize == 1 ? 1 : d.dilation;   // (a 1x1 layer has no dilation)
+    const int index = d.ksize == 1 ? 4 : (d.ksize != 3 ? -1 : (dil == 1 ? 0 : (dil == 2 ? 1 : (dil == 4 ? 2 : (dil == 8 ? 3 : -1)))));
+    if (index < 0) return refuse(DMB_EUNSUPPORTED, "conv2d_wgrad: kernel 1, or kernel 3 with dilation 1, 2, 4 or 8 (stride 1)");
+    // y segments of a row class (rows y, y + dil, ...: cdiv(H, dil) of them); two workgroups per CU
+    const int ntx = cdiv(W, Wg2dCfg<3, 1>::TX), HC = cdiv(H, dil), nslots = wgrad_slots_per_block(Co, Ci, 2, ncu);
+    const long long per_seg = (long long)B * ntx * dil;
+    return planned(WGRAD_2D, index, ntx, dil, HC, segment_search(HC, per_seg, nslots, WG_SEG_2D), per_seg, nslots);
+  }
+  return refuse(DMB_EINVAL, "conv_wgrad_plan: kind must be DMB_WGRAD_S1, DMB_WGRAD_S2 or DMB_WGRAD_2D");
+}
+
 }  // namespace dmb
 
-static int wgrad2d_slots_per_block(int Co, int Ci) {
-  const int nblk = cdiv(Co, 32) * cdiv(Ci, 32);
-  const int s = 2 * wgrad_slots() / nblk;   // two workgroups per CU
-  return s < 1 ? 1 : s;
-}
+using namespace dmb;
 
-extern "C" long long dmb_conv2d_wgrad_workspace_floats(int Co, int Ci) {
-  if (Co <= 0 || Ci <= 0) return 0;
-  return (long long)cdiv(Co, 32) * cdiv(Ci, 32) * wgrad2d_slots_per_block(Co, Ci) * 9 * 1024;
-}
+extern "C" long long dmb_conv3d_wgrad_workspace_floats(int Co, int Ci) { return Co <= 0 || Ci <= 0 ? 0 : wgrad_ws_floats(Co, Ci, 1, 27, num_cus()); }
+extern "C" long long dmb_conv2d_wgrad_workspace_floats(int Co, int Ci) { return Co <= 0 || Ci <= 0 ? 0 : wgrad_ws_floats(Co, Ci, 2, 9, num_cus()); }
 
-template <int KS, int DIL>
-static int launch_wgrad2d(const float* x, const float* dc, float* dw, float* workspace, int B, int Ci, int Co, int H, int W, hipStream_t st) {
-  typedef Wg2dCfg<KS, DIL> C;
-  const int nblk = cdiv(Co, 32) * cdiv(Ci, 32), nslots = wgrad2d_slots_per_block(Co, Ci);
-  const int ntx = cdiv(W, C::TX);
-  const int HC = cdiv(H, DIL);   // rows of one row class
-  int yseg = HC;
-  {
-    double best = 1e30;
-    for (int ny = 1; ny <= HC; ++ny) {
-      const int ysz = cdiv(HC, ny);
-      if (ysz < 8 && ny > 1) break;
-      const double cost = (double)cdiv_ll((long long)B * ntx * DIL * cdiv(HC, ysz), nslots) * (ysz + 2.0);
-      if (cost < best - 1e-9) {
-        best = cost;
-        yseg = ysz;
-      }
-    }
+extern "C" int dmb_conv_wgrad_plan(int kind, int B, int Co, int Ci, int D, int H, int W, int Db, int Hb, int Wb, int ksize, int dilation,
+                                   int align, int ncu, int* detail_host) {
+  WgradPlan p = {};
+  const char* why = "";
+  const int rc = wgrad_plan({kind, B, Co, Ci, D, H, W, Db, Hb, Wb, ksize, dilation, align, ncu > 0 ? ncu : num_cus()}, &p, &why);
+  set_last_error(why);
+  if (rc != DMB_OK) return -rc;
+  if (detail_host) {
+    const int v[6] = {p.ntx, p.nty, p.seg, p.nseg, p.slots, p.blocks};
+    for (int i = 0; i < 6; ++i) detail_host[i] = v[i];
   }
-  const int nys = cdiv(HC, yseg);
-  DMB_ENSURE_LDS((&conv2d_wgrad_kernel<KS, DIL>), (size_t)(C::LDS_FLOATS * 4));
-  const long long items = (long long)B * ntx * DIL * nys;
-  const int nused = (int)(items < nslots ? items : nslots);   // small layers: no idle slots to write and add zeros for
-  hipLaunchKernelGGL((conv2d_wgrad_kernel<KS, DIL>), dim3((unsigned)nused, (unsigned)nblk), dim3(256), C::LDS_FLOATS * 4, st, x, dc, workspace, B,
-                     Ci, Co, H, W, ntx, nys, yseg);
-  int rc = launch_status("conv2d_wgrad launch failed");
+  return p.code;
+}
+
+// the two operands' alignment together
+static int align_of_both(const void* a, const void* b) { return align_of(reinterpret_cast<const void*>((uintptr_t)a | (uintptr_t)b)); }
+
+extern "C" int dmb_conv3d_k3_wgrad_f32(const float* x, const float* dc, float* dw, float* workspace, int B, int Ci, int Co,
+                                       int D, int H, int W, void* stream) {
+  if (!x || !dc || !dw || !workspace) return fail(DMB_EINVAL, "conv3d_wgrad: bad argument");
+  WgradPlan p;
+  const char* why = "";
+  int rc = wgrad_plan({DMB_WGRAD_S1, B, Co, Ci, D, H, W, 0, 0, 0, 3, 1, align_of_both(x, dc), num_cus()}, &p, &why);
+  if (rc != DMB_OK) return fail(rc, why);
+  hipStream_t st = (hipStream_t)stream;
+  if (p.code >> 8 == WGRAD_C1) {
+    hipLaunchKernelGGL(conv3d_c1_wgrad_kernel, dim3((unsigned)p.slots, (unsigned)p.blocks), dim3(256), 0, st, x, dc, workspace, B, Ci, D, H, W, p.ntx,
+                       p.nty, B * p.nseg * p.ntx * p.nty);
+    hipLaunchKernelGGL(conv3d_c1_wgrad_reduce_kernel, dim3(cdiv(Ci * 27, 4)), dim3(256), 0, st, workspace, dw, Ci, p.slots);
+    return launch_status("conv3d_wgrad (1 channel) launch failed");
+  }
+  rc = wg_visit<WgS1Forms>(p.code, [&](auto f) {
+    typedef decltype(f) F;
+    static unsigned long long seen = 0;
+    return wg_launch(&conv3d_wgrad_s1_kernel<F::V16, F::C::TX>, F::C::LDS_FLOATS * 4, &seen, p, st, "conv3d_wgrad launch failed", x, dc, workspace,
+                     B, Ci, Co, D, H, W, p.ntx, p.nty, p.nseg, p.seg);
+  });
   if (rc != DMB_OK) return rc;
-  hipLaunchKernelGGL(conv2d_wgrad_reduce_kernel, dim3(cdiv(nblk * C::NTAP * 1024, 256)), dim3(256), 0, st, workspace, dw, Co, Ci, nused, C::NTAP);
-  return launch_status("conv2d_wgrad reduce launch failed");
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(p.blocks * 27 * 16), dim3(256), 0, st, workspace, dw, Co, Ci, p.slots);
+  return launch_status("conv3d_wgrad reduce launch failed");
+}
+
+extern "C" int dmb_conv3d_k3s2_wgrad_f32(const float* small, const float* big, float* dw, float* workspace, int B, int Cs, int Cb,
+                                         int Ds, int Hs, int Ws, int Db, int Hb, int Wb, void* stream) {
+  if (!small || !big || !dw || !workspace) return fail(DMB_EINVAL, "conv3d_s2_wgrad: bad argument");
+  WgradPlan p;
+  const char* why = "";
+  int rc = wgrad_plan({DMB_WGRAD_S2, B, Cs, Cb, Ds, Hs, Ws, Db, Hb, Wb, 3, 1, align_of_both(small, big), num_cus()}, &p, &why);
+  if (rc != DMB_OK) return fail(rc, why);
+  hipStream_t st = (hipStream_t)stream;
+  rc = wg_visit<WgS2Forms>(p.code, [&](auto f) {
+    typedef decltype(f) F;
+    static unsigned long long seen = 0;
+    return wg_launch(&conv3d_wgrad_s2_kernel<typename F::C, F::V16>, F::C::LDS_FLOATS * 4, &seen, p, st, "conv3d_s2_wgrad launch failed", small, big,
+                     workspace, B, Cs, Cb, Ds, Hs, Ws, Db, Hb, Wb, p.ntx, p.nty, p.nseg, p.seg);
+  });
+  if (rc != DMB_OK) return rc;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(p.blocks * 27 * 16), dim3(256), 0, st, workspace, dw, Cs, Cb, p.slots);
+  return launch_status("conv3d_s2_wgrad reduce launch failed");
 }
 
 extern "C" int dmb_conv2d_wgrad_f32(const float* x, const float* dc, float* dw, float* workspace, int B, int Ci, int Co, int H, int W,
                                     int ksize, int dilation, void* stream) {
-  if (!x || !dc || !dw || !workspace || B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0) return fail(DMB_EINVAL, "conv2d_wgrad: bad argument");
-  if ((long long)32 * H * W * 4 >= 0x7fffffffLL) return fail(DMB_EUNSUPPORTED, "conv2d_wgrad: 32 channels of one image must stay below 2 GiB");
-  if (W % 4 != 0 || (((uintptr_t)x | (uintptr_t)dc) & 15) != 0)
-    return fail(DMB_EUNSUPPORTED, "conv2d_wgrad: the width must be a multiple of 4 and the tensors 16-byte aligned");
+  if (!x || !dc || !dw || !workspace) return fail(DMB_EINVAL, "conv2d_wgrad: bad argument");
+  WgradPlan p;
+  const char* why = "";
+  const int rc = wgrad_plan({DMB_WGRAD_2D, B, Co, Ci, 1, H, W, 0, 0, 0, ksize, dilation, align_of_both(x, dc), num_cus()}, &p, &why);
+  if (rc != DMB_OK) return fail(rc, why);
   hipStream_t st = (hipStream_t)stream;
-  if (ksize == 3 && dilation == 1) return launch_wgrad2d<3, 1>(x, dc, dw, workspace, B, Ci, Co, H, W, st);
-  if (ksize == 3 && dilation == 2) return launch_wgrad2d<3, 2>(x, dc, dw, workspace, B, Ci, Co, H, W, st);
-  if (ksize == 3 && dilation == 4) return launch_wgrad2d<3, 4>(x, dc, dw, workspace, B, Ci, Co, H, W, st);
-  if (ksize == 3 && dilation == 8) return launch_wgrad2d<3, 8>(x, dc, dw, workspace, B, Ci, Co, H, W, st);
-  if (ksize == 1) return launch_wgrad2d<1, 1>(x, dc, dw, workspace, B, Ci, Co, H, W, st);
-  return fail(DMB_EUNSUPPORTED, "conv2d_wgrad: kernel 1, or kernel 3 with dilation 1, 2, 4 or 8 (stride 1)");
+  return wg_visit<Wg2dForms>(p.code, [&](auto c) {
+    typedef decltype(c) C;
+    static unsigned long long seen = 0;
+    const int lrc = wg_launch(&conv2d_wgrad_kernel<C::KS, C::DIL>, C::LDS_FLOATS * 4, &seen, p, st, "conv2d_wgrad launch failed", x, dc, workspace, B, Ci,
+                              Co, H, W, p.ntx, p.nseg, p.seg);
+    if (lrc != DMB_OK) return lrc;
+    hipLaunchKernelGGL(conv2d_wgrad_reduce_kernel, dim3(cdiv(p.blocks * C::NTAP * 1024, 256)), dim3(256), 0, st, workspace, dw, Co, Ci, p.slots, C::NTAP);
+    return launch_status("conv2d_wgrad reduce launch failed");
+  });
 }
+

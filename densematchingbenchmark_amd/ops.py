@@ -951,6 +951,33 @@ def conv2d_k3_wgrad(x, dc):
     return conv2d_wgrad(x, dc, 3, 1)
 
 
+WGRAD_PLAN_S1, WGRAD_PLAN_S2, WGRAD_PLAN_C1, WGRAD_PLAN_2D = 1, 2, 3, 4   # dmb_conv_wgrad_plan: the form, bits 8.. of a plan code
+
+
+def conv_wgrad_plan(kind, a, b, ksize=3, dilation=1, ncu=0):
+    """What a weight-gradient wrapper would launch: ``(code, detail)`` of dmb_conv_wgrad_plan (include/dmb_hip.h) -- the plan code
+    (form << 8) | index, or minus the DMB_E* code of a refusal, and the six numbers (tiles along x, along y, segment length,
+    segments, slots, channel blocks).  ``kind``/``a``/``b``: ``_lib.DEFINES["DMB_WGRAD_S1"]`` with ``conv3d_k3_wgrad``'s (x, dc);
+    ``DMB_WGRAD_S2`` with (small, big) = (dc, x) of ``conv3d_k3s2_wgrad`` or (x, dy) of ``deconv3d_k3s2_wgrad``; ``DMB_WGRAD_2D``
+    with ``conv2d_wgrad``'s (x, dc) after its padding of W % 4.  Either may be a shape: it then counts as 16-byte aligned.
+    ``ncu``: compute units to plan for, 0 = the current device's."""
+    D = _lib.DEFINES
+    sa, sb = (tuple(int(v) for v in (t if isinstance(t, (tuple, list)) else t.shape)) for t in (a, b))
+    align = min(_align(None if isinstance(a, (tuple, list)) else a), _align(None if isinstance(b, (tuple, list)) else b))
+    if kind == D["DMB_WGRAD_2D"]:
+        (B, Ci, H, W), Co = sa, sb[1]
+        dims = (1, H, W, 0, 0, 0)
+    elif kind == D["DMB_WGRAD_S2"]:
+        (B, Co), Ci = sa[:2], sb[1]
+        dims = sa[2:] + sb[2:]
+    else:
+        (B, Ci), Co = sa[:2], sb[1]
+        dims = sa[2:] + (0, 0, 0)
+    detail = (ctypes.c_int * 6)()
+    code = _lib.load().dmb_conv_wgrad_plan(int(kind), B, Co, Ci, *dims, int(ksize), int(dilation), align, int(ncu), detail)
+    return code, tuple(detail)
+
+
 def conv2d_dgrad_packs(w, dilation=1):
     """Packed weights of the data-gradient convolution of a stride-1 nn.Conv2d with weight [Co, Ci, k, k]: the layer's taps mirrored,
     channel roles exchanged, in chunks of output (= the layer's input) channels that dmb_conv2d_f32 launches: at most 128, never

@@ -44,13 +44,13 @@ extern "C" {
 
 #define DMB_MAX_DISP_SAMPLES 256 /* upper bound on the number of disparity samples D */
 
-/* ABI version: bumped whenever a signature below changes (11: dmb_conv2d_plan added; 10: dmb_conv3d_k3_plan added; 9: dmb_deconv3d_k3s2_plan added; 8: dmb_bn_train_fwd_f32, dmb_catconv_pack_weights_f32, dmb_conv3d_pack_weights_multi_f32, dmb_cat_first_wgrad_maps_f32, dmb_conv3d_k3_bnstats_f32 and dmb_bn_train_act_f32 added, dmb_bn_act_bwd_f32 takes the gradient its
+/* ABI version: bumped whenever a signature below changes (12: dmb_conv_wgrad_plan added; 11: dmb_conv2d_plan added; 10: dmb_conv3d_k3_plan added; 9: dmb_deconv3d_k3s2_plan added; 8: dmb_bn_train_fwd_f32, dmb_catconv_pack_weights_f32, dmb_conv3d_pack_weights_multi_f32, dmb_cat_first_wgrad_maps_f32, dmb_conv3d_k3_bnstats_f32 and dmb_bn_train_act_f32 added, dmb_bn_act_bwd_f32 takes the gradient its
  * skip operand already holds (`dres_acc`); 7: DMB_CONV_SINGLE_CHAIN in the `relu` argument of the convolution
  * entry points, `flags` argument of dmb_conv3d_k3_c1_f32; 6: dmb_stereo_pad_normalize_f32 / _u8 added; 5: dmb_fast_fms_bwd_f32 takes a mode, the forward's norm and an
  * optional gradient buffer for per-pixel samples; 4: workspace argument of dmb_deconv3d_k3s2_f32, the merged-heads entry
  * points of version 3 removed).  The define is the one place the number is written: dmb_abi_version() returns it and the Python
  * binding reads it from this file. */
-#define DMB_ABI_VERSION 11
+#define DMB_ABI_VERSION 12
 int dmb_abi_version(void);
 /* Static string describing the last DMB_E* code returned on this thread ("" if none). */
 const char* dmb_last_error(void);
@@ -627,6 +627,31 @@ int dmb_conv3d_k3s2_wgrad_f32(const float* small, const float* big, float* dw, f
 long long dmb_conv2d_wgrad_workspace_floats(int Co, int Ci);
 int dmb_conv2d_wgrad_f32(const float* x, const float* dc, float* dw, float* workspace, int B, int Ci, int Co, int H, int W,
                          int ksize, int dilation, void* stream);
+
+/* What the three weight-gradient entry points above would run for a launch, without launching anything or touching a device: a pure
+ * function of its arguments, in the conventions of dmb_conv3d_k3_plan (csrc/wgrad_plan.h).  kind: which entry point --
+ *   DMB_WGRAD_S1  dmb_conv3d_k3_wgrad_f32:    Co / Ci = channels of dc / x, D, H, W their extents (Db, Hb, Wb, ksize, dilation unused)
+ *   DMB_WGRAD_S2  dmb_conv3d_k3s2_wgrad_f32:  Co / Ci = Cs / Cb, D, H, W = the small operand's extents, Db, Hb, Wb the big one's
+ *   DMB_WGRAD_2D  dmb_conv2d_wgrad_f32:       Co / Ci = channels of dc / x, H, W, ksize, dilation (D, Db, Hb, Wb unused)
+ * align: the alignment in bytes of the two operands together (of the bitwise OR of their addresses; 16 or more = 16-byte aligned);
+ * ncu: compute units to plan for, <= 0 = the current device's (256 where there is none).  Returns (form << 8) | index:
+ *   form 1  stride 1, tiles of 4 rows x TX columns walked along z:  0 = 24 columns, 16-byte staging;  1 = 32 columns, 16-byte staging
+ *           (where 32-column tiles cover W with fewer computed columns);  2 = 24 columns, dword staging (W % 4 != 0 or align < 16)
+ *   form 2  stride 2, tiles of TY x TX voxels of the small operand:  0 / 1 = 2 x 12 with 16-byte / dword staging,  2 / 3 = 4 x 8 with
+ *           16-byte / dword staging (dword: either width % 4 != 0 or align < 16); 4 x 8 where its estimated cost -- rounds of the grid
+ *           x (planes per segment + 1) x tile voxels / 1.1 -- is below that of 2 x 12
+ *   form 3  stride 1 with ONE output channel (Co == 1):  0
+ *   form 4  2-D, strips of 64 columns walked along y:  0 .. 3 = kernel 3 with dilation 1, 2, 4, 8;  4 = kernel 1
+ * or -DMB_EINVAL / -DMB_EUNSUPPORTED where the launch would be refused with that code (dmb_last_error() then names the reason).
+ * detail_host: NULL, or 6 host ints that receive the rest of the plan: tiles along x, tiles along y (2-D: the row classes = the dilation),
+ * planes (2-D: rows of a class) per segment, segments (form 3: 1 and D), workgroup slots per channel block (grid x; form 3: the
+ * workgroups), 32 x 32 channel blocks (grid y).  items = B x tiles x segments; slots x blocks x taps x 1024 floats (form 3: slots x Ci x 27) never
+ * exceed dmb_*_wgrad_workspace_floats(Co, Ci). */
+#define DMB_WGRAD_S1 1
+#define DMB_WGRAD_S2 2
+#define DMB_WGRAD_2D 4
+int dmb_conv_wgrad_plan(int kind, int B, int Co, int Ci, int D, int H, int W, int Db, int Hb, int Wb, int ksize, int dilation, int align,
+                        int ncu, int* detail_host);
 
 /* BatchNorm (training mode) + skip add + ReLU of a convolution unit, layout [B, C, S] (S = voxels or pixels per channel).
  * relu: 0 none, 1 after the skip add, 2 before it -- the same epilogue the inference kernels fuse.
