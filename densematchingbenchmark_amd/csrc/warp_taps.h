@@ -70,4 +70,15 @@ __device__ inline float warp_blend(const WarpTaps& t, const float* __restrict__ 
   return acc;
 }
 
+// warp_blend on four image values the caller has loaded already, v[q] = plane[t.off[q]] (an out-of-range tap's offset is 0, a
+// valid address; its value is not used): the same accumulation, for callers that issue the loads of several planes at once
+#pragma clang fp contract(off)
+__device__ inline float warp_blend_loaded(const WarpTaps& t, const float v[4]) {
+  float acc = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+    if (t.valid >> i & 1u) acc = (acc + (v[i & 3] * t.w[i]));
+  return acc;
+}
+
 }  // namespace dmb

@@ -3,7 +3,8 @@
 Stage "pre": differentiable PatchMatch over the full range [0, max_disp] -- ``2 * iterations`` launches of one fused
 propagate + evaluate kernel (dmb_patch_match_step_f32), the last of which writes the [B, P + 2, H, W] result with both ends of
 the range in place.  Stage "post": the range head and the uniform sampler in one elementwise launch
-(dmb_deeppruner_uniform_samples_f32).  No parameters, inference only: the backward of PatchMatch is not built.
+(dmb_deeppruner_uniform_samples_f32).  No parameters.  These modules are inference only; the differentiable path is
+``layers.train_fn.deeppruner_sampler(sampler, stage, ...)`` on the same kernels and their backward (docs/design/14).
 
 The reference draws PatchMatch's initial noise inside the module; here ``noise=None`` draws it from torch's device generator
 (``torch.manual_seed`` reproduces a call) and a given ``noise`` tensor [B, P, H, W] is used as it is and left untouched.
@@ -16,8 +17,9 @@ from .... import ops
 
 def _refuse_gradients(what, *tensors):
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors):
-        raise NotImplementedError("%s: an input requires a gradient, but the backward of PatchMatch / the disparity sampler is "
-                                  "not implemented on the HIP path (inference only: call it under torch.no_grad())" % what)
+        raise NotImplementedError("%s: an input requires a gradient, but this module is inference only (call it under "
+                                  "torch.no_grad()); the backward of PatchMatch / the disparity sampler is reached through "
+                                  "layers.train_fn.deeppruner_sampler(sampler, stage, ...)" % what)
 
 
 class DisparitySampleRangeHead(nn.Module):

@@ -22,7 +22,7 @@ import weakref
 
 import torch
 
-from .... import ops, param_state
+from .... import ops, ops_deeppruner, param_state
 
 _RELU = {0: False, 1: True, 2: "pre"}
 _CONST = {}
@@ -853,6 +853,117 @@ class SoftArgminFn(torch.autograd.Function):
     def backward(ctx, ddisp):
         cost, disp = ctx.saved_tensors
         return ops.soft_argmin_bwd(cost, disp, ddisp.contiguous(), list(ctx.values), ctx.alpha), None, None
+
+
+# ---------------------------------------------------------------------------------------------- DeepPruner's sampler
+PATCH_MATCH_BWD_MAX_W = 1024   # dmb_patch_match_step_bwd_f32 (DMB_PATCH_MATCH_BWD_MAX_W): 8 channel rows of W floats in LDS
+
+
+def _refuse_double_backward(what):
+    """Called first thing in a ``backward``.  Grad mode is on there only when the caller asked for a graph of the backward itself
+    (``create_graph=True``): the launches below record none, so a second-order term would be dropped silently -- whether or not
+    the upstream gradient itself requires one (a gradient penalty's does not).  Refuse instead."""
+    if torch.is_grad_enabled():
+        raise NotImplementedError("%s: double backward (a gradient of the gradient, create_graph=True) is not implemented on the "
+                                  "HIP path" % what)
+
+
+def _refuse_cpu(what, *tensors):
+    for t in tensors:
+        if isinstance(t, torch.Tensor) and not t.is_cuda:
+            raise ops._lib.DmbLibraryError("%s: an operand lives on %s: the dmb HIP path only runs on a GPU (cuda/hip) tensor and "
+                                           "has no CPU fallback" % (what, t.device))
+
+
+class PatchMatchFn(torch.autograd.Function):
+    """PatchMatch (disp_samplers/utils/patch_match.py:305-361) under autograd on csrc/patch_match.hip.  The forward is
+    PatchMatch.forward's ``2 * iterations`` launches (the same bits) and keeps the [B, P, H, W] noise ENTERING each half-iteration
+    -- nothing else; the backward runs dmb_patch_match_step_bwd_f32 over the steps in reverse, each recomputing its candidates
+    and costs from that noise, and returns the gradients of ``left``, ``right`` and the initial ``noise`` (the last d_noise_in).
+    The range is the constant ``bounds``, or two [B, 1, H, W] maps taken as constants (no gradient for them)."""
+
+    @staticmethod
+    def forward(ctx, left, right, noise, min_disparity, max_disparity, bounds, iterations, temperature):
+        B, _, H, W = left.shape
+        P = noise.shape[1]
+        out = torch.empty((B, P + 2, H, W), dtype=torch.float32, device=left.device)
+        steps, noises = 2 * int(iterations), []
+        for step in range(steps):
+            last = step == steps - 1
+            noises.append(noise)
+            _, noise = ops.patch_match_step(left, right, noise, min_disparity, max_disparity, vertical=step % 2 == 1,
+                                            temperature=temperature, bounds=bounds, want_noise=not last, out=out if last else None)
+        ctx.has_maps = min_disparity is not None
+        ctx.save_for_backward(left, right, *(((min_disparity, max_disparity) if ctx.has_maps else ()) + tuple(noises)))
+        ctx.bounds, ctx.temperature = tuple(bounds), temperature
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        _refuse_double_backward("PatchMatch")
+        left, right = ctx.saved_tensors[:2]
+        lo, hi = ctx.saved_tensors[2:4] if ctx.has_maps else (None, None)
+        noises = ctx.saved_tensors[4 if ctx.has_maps else 2:]
+        dL = dR = None
+        gS, gN = dout.contiguous(), None     # [B, P + 2, H, W]: the two ends are the range, constants here
+        for step in range(len(noises) - 1, -1, -1):
+            dL, dR, gN = ops_deeppruner.patch_match_step_bwd(left, right, noises[step], lo, hi, grad_samples=gS, grad_noise=gN,
+                                                  vertical=step % 2 == 1, temperature=ctx.temperature, bounds=ctx.bounds,
+                                                  grad_left_acc=dL, grad_right_acc=dR)
+            gS = None                        # only the last half-iteration's samples are an output
+        need = ctx.needs_input_grad
+        return (dL if need[0] else None, dR if need[1] else None, gN if need[2] else None, None, None, None, None, None)
+
+
+class UniformSamplesFn(torch.autograd.Function):
+    """Stage "post" (DeepPruner.py:48-66, 99-115) under autograd: dmb_deeppruner_uniform_samples_f32 and its backward, one
+    elementwise launch each."""
+
+    @staticmethod
+    def forward(ctx, min_disparity, max_disparity, sample_number, max_disp):
+        ctx.save_for_backward(min_disparity, max_disparity)
+        ctx.max_disp = max_disp
+        return ops.deeppruner_uniform_samples(min_disparity, max_disparity, sample_number, max_disp)
+
+    @staticmethod
+    def backward(ctx, dout):
+        _refuse_double_backward("UniformSampler")
+        lo, hi = ctx.saved_tensors
+        glo, ghi = ops_deeppruner.deeppruner_uniform_samples_bwd(lo, hi, dout.contiguous(), ctx.max_disp)
+        return (glo if ctx.needs_input_grad[0] else None, ghi if ctx.needs_input_grad[1] else None, None, None)
+
+
+def deeppruner_sampler(sampler, stage, left, right, min_disparity=None, max_disparity=None, noise=None):
+    """Differentiable forward of a DeepPrunerSampler (whose own ``forward`` stays inference only): stage "pre" is PatchMatch over
+    [0, max_disp] with gradients for ``left``, ``right`` and ``noise``; any other stage is the range head and the uniform sampler
+    with gradients for the two maps.  Counts, temperature, iterations and ``max_disp`` are the sampler's."""
+    if stage == 'pre':
+        if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (min_disparity, max_disparity)):
+            raise NotImplementedError("deeppruner_sampler: stage 'pre' ignores the range maps (DeepPruner.py:176-184); a gradient "
+                                      "for PatchMatch's range is not implemented on the HIP path")
+        pm = sampler.patch_match
+        if left.dim() != 4:
+            raise ValueError("PatchMatch: features must be [B, C, H, W], got %s" % (tuple(left.shape),))
+        B, _, H, W = left.shape
+        if H < 2 or W < 2:
+            raise NotImplementedError("PatchMatch: H, W >= 2 (the reference divides by size - 1), got %dx%d" % (H, W))
+        if W > PATCH_MATCH_BWD_MAX_W:   # refuse here, not inside backward()
+            raise NotImplementedError("PatchMatch under autograd: feature maps wider than %d columns have no backward on the HIP "
+                                      "path (the forward alone has no such limit: run it under torch.no_grad())"
+                                      % PATCH_MATCH_BWD_MAX_W)
+        P = pm.disparity_sample_number - 2
+        if noise is not None:
+            noise = pm.check_noise(noise, left)
+        _refuse_cpu("deeppruner_sampler", left, right)
+        if noise is None:
+            noise = torch.rand((B, P, H, W), dtype=torch.float32, device=left.device)
+        return PatchMatchFn.apply(left.contiguous(), right.contiguous(), noise.contiguous(), None, None,
+                                  (0.0, float(sampler.max_disp)), pm.iterations, pm.temperature)
+    if min_disparity is None or max_disparity is None:
+        raise ValueError("DeepPrunerSampler: stage %r needs min_disparity and max_disparity" % (stage,))
+    _refuse_cpu("deeppruner_sampler", min_disparity, max_disparity)
+    return UniformSamplesFn.apply(min_disparity.contiguous(), max_disparity.contiguous(),
+                                  sampler.uniform_sampler.disparity_sample_number, sampler.max_disp)
 
 
 def wants_grad(module, *tensors):

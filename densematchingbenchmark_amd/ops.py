@@ -1955,4 +1955,17 @@ def deeppruner_uniform_samples(min_disparity, max_disparity, sample_number, max_
     return out
 
 
+def __getattr__(name):
+    """The sampler's two backward wrappers live in ``ops_deeppruner`` (this module's launching functions are an enumerated set,
+    tests/test_memory_contract_gpu.py); ``ops.patch_match_step_bwd`` and ``ops.deeppruner_uniform_samples_bwd`` name them."""
+    if name in ("patch_match_step_bwd", "deeppruner_uniform_samples_bwd"):
+        from . import ops_deeppruner
+        return getattr(ops_deeppruner, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
+def __dir__():
+    return sorted(list(globals()) + ["patch_match_step_bwd", "deeppruner_uniform_samples_bwd"])
+
+
 from .spn import GateRecurrent2dnoind  # noqa: E402,F401  (``dmb.ops.GateRecurrent2dnoind``: dmb/ops/__init__.py:1)

@@ -10,7 +10,7 @@ import torch
 
 from . import _lib
 from ._lib import launch, opt
-from .ops import _f32c, _feature_pair, _same_shape
+from .ops import _f32c, _feature_pair, _range_maps, _same_shape
 
 K5_MAX_C = _lib.DEFINES["DMB_CONV2D_K5_MAX_C"]
 MAX_FEATURE_PLANES = _lib.DEFINES["DMB_PATCH_MATCH_MAX_SAMPLES"]
@@ -201,4 +201,79 @@ def quantile_loss_bwd(min_disparity, max_disparity, gt, stats, grad_out, q_lower
     glo = torch.empty(tuple(gt.shape), dtype=torch.float32, device=gt.device)
     ghi = torch.empty(tuple(gt.shape), dtype=torch.float32, device=gt.device)
     launch("dmb_quantile_loss_bwd_f32", lo, hi, gt, stats, go, glo, ghi, gt.shape[0], gt.shape[2], gt.shape[3], q_lower, q_upper, theta)
+    return glo, ghi
+
+
+# ---------------------------------------------------------------------------------------------- the sampler's backward
+# csrc/patch_match.hip; ``ops.patch_match_step_bwd`` and ``ops.deeppruner_uniform_samples_bwd`` resolve to these two (ops.__getattr__).
+# Their memory-contract cases are in tests/test_memory_contract_deeppruner_sampler_bwd_gpu.py.
+PATCH_MATCH_BWD_MAX_W = _lib.DEFINES["DMB_PATCH_MATCH_BWD_MAX_W"]
+
+
+def patch_match_step_bwd(left, right, noise, min_disparity=None, max_disparity=None, grad_samples=None, grad_noise=None,
+                         vertical=False, temperature=7.0, bounds=(0.0, 0.0), grad_left_acc=None, grad_right_acc=None):
+    """Backward of ``ops.patch_match_step`` for the same ``left``, ``right``, ``noise`` (the step's INPUT noise), range and
+    ``vertical``: returns (d left, d right, d noise), [B, C, H, W] x 2 and [B, P, H, W].  ``grad_samples``: the gradient of the
+    step's samples, [B, P, H, W] or the [B, P + 2, H, W] of ``patch_match_step(out=)`` (channels 1 .. P are read);
+    ``grad_noise``: the gradient of the step's new noise, [B, P, H, W]; either may be None (zero), not both.
+    ``grad_left_acc`` / ``grad_right_acc``: [B, C, H, W] added into the two feature gradients (read, not modified).  The range
+    maps are constants here: they get no gradient.  No host copy, no synchronisation."""
+    left, right = _feature_pair(left, right, "patch_match_step_bwd")
+    noise = _f32c(noise, "noise")
+    B, C, H, W = left.shape
+    if noise.dim() != 4 or noise.shape[0] != B or tuple(noise.shape[2:]) != (H, W):
+        raise _lib.DmbLibraryError("patch_match_step_bwd: noise must be [%d, P, %d, %d], got %s" % (B, H, W, tuple(noise.shape)))
+    P = noise.shape[1]
+    if W > PATCH_MATCH_BWD_MAX_W:
+        raise NotImplementedError("patch_match_step_bwd: feature maps wider than %d columns have no backward on the HIP path, got %d"
+                                  % (PATCH_MATCH_BWD_MAX_W, W))
+    if (min_disparity is None) != (max_disparity is None):
+        raise _lib.DmbLibraryError("patch_match_step_bwd: give both range maps or neither")
+    lo = hi = None
+    if min_disparity is not None:
+        lo, hi = _range_maps(min_disparity, max_disparity, B, H, W, "patch_match_step_bwd")
+    if grad_samples is None and grad_noise is None:
+        raise _lib.DmbLibraryError("patch_match_step_bwd: neither grad_samples nor grad_noise")
+    ctot = coff = 0
+    if grad_samples is not None:
+        grad_samples = _f32c(grad_samples, "grad_samples")
+        if tuple(grad_samples.shape) == (B, P, H, W):
+            ctot, coff = P, 0
+        elif tuple(grad_samples.shape) == (B, P + 2, H, W):
+            ctot, coff = P + 2, 1
+        else:
+            raise _lib.DmbLibraryError("patch_match_step_bwd: grad_samples must be [%d, %d | %d, %d, %d], got %s"
+                                       % (B, P, P + 2, H, W, tuple(grad_samples.shape)))
+    if grad_noise is not None:
+        grad_noise = _f32c(grad_noise, "grad_noise")
+        _same_shape(grad_noise, noise, "patch_match_step_bwd grad_noise")
+    for t, n in ((grad_left_acc, "grad_left_acc"), (grad_right_acc, "grad_right_acc")):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (B, C, H, W)):
+            raise _lib.DmbLibraryError("patch_match_step_bwd: %s must be a contiguous float32 [%d, %d, %d, %d]" % (n, B, C, H, W))
+    dl = torch.empty((B, C, H, W), dtype=torch.float32, device=left.device)
+    dr = torch.empty((B, C, H, W), dtype=torch.float32, device=left.device)
+    dn = torch.empty((B, P, H, W), dtype=torch.float32, device=left.device)
+    ws = torch.empty((6 * B * P * H * W + 2 * B * C * H * W,), dtype=torch.float32, device=left.device)
+    launch("dmb_patch_match_step_bwd_f32", left, right, noise, opt(lo), opt(hi), bounds[0], bounds[1], opt(grad_samples),
+           opt(grad_noise), opt(grad_left_acc), opt(grad_right_acc), dl, dr, dn, ws, B, C, P, H, W, int(bool(vertical)), temperature,
+           ctot, coff)
+    return dl, dr, dn
+
+
+def deeppruner_uniform_samples_bwd(min_disparity, max_disparity, grad_out, max_disp=None):
+    """Backward of ``ops.deeppruner_uniform_samples``: ``grad_out`` [B, N, H, W] -> (d min_disparity, d max_disparity),
+    [B, 1, H, W] each, through the uniform sampler and -- with ``max_disp`` -- the range head, with torch's subgradients at ties
+    and clamp edges.  One launch, every element written once."""
+    lo = _f32c(min_disparity, "min_disparity")
+    if lo.dim() != 4 or lo.shape[1] != 1:
+        raise _lib.DmbLibraryError("deeppruner_uniform_samples_bwd: min_disparity must be [B, 1, H, W], got %s" % (tuple(lo.shape),))
+    B, _, H, W = lo.shape
+    lo, hi = _range_maps(lo, max_disparity, B, H, W, "deeppruner_uniform_samples_bwd")
+    go = _f32c(grad_out, "grad_out")
+    if go.dim() != 4 or go.shape[0] != B or tuple(go.shape[2:]) != (H, W):
+        raise _lib.DmbLibraryError("deeppruner_uniform_samples_bwd: grad_out must be [%d, N, %d, %d], got %s" % (B, H, W, tuple(go.shape)))
+    glo = torch.empty((B, 1, H, W), dtype=torch.float32, device=lo.device)
+    ghi = torch.empty((B, 1, H, W), dtype=torch.float32, device=lo.device)
+    launch("dmb_deeppruner_uniform_samples_bwd_f32", lo, hi, go, glo, ghi, B, H, W, go.shape[1], max_disp is not None,
+           max_disp if max_disp is not None else 0.0)
     return glo, ghi

@@ -807,7 +807,7 @@ int dmb_anynet_final_maps_f32(const float* d0, const float* d1, const float* d2,
                               const int* w_host, float* out, int B, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * DeepPruner's disparity sampler (disp_samplers/DeepPruner.py, disp_samplers/utils/patch_match.py), forward only
+ * DeepPruner's disparity sampler (disp_samplers/DeepPruner.py, disp_samplers/utils/patch_match.py), forward and backward
  * ---------------------------------------------------------------------------------------- */
 
 #define DMB_PATCH_MATCH_MAX_SAMPLES 85 /* intervals P of one PatchMatch step: 3P planes <= DMB_MAX_DISP_SAMPLES */
@@ -838,6 +838,40 @@ int dmb_patch_match_step_f32(const float* L, const float* R, const float* noise_
  * Elementwise FP32 in the reference's order of operations: bit-exact.  2 <= N <= DMB_MAX_DISP_SAMPLES. */
 int dmb_deeppruner_uniform_samples_f32(const float* min_disp, const float* max_disp, float* out, int B, int H, int W, int N,
                                        int range_head, float max_disp_limit, void* stream);
+
+#define DMB_PATCH_MATCH_BWD_MAX_W 1024 /* columns of dmb_patch_match_step_bwd_f32: 8 channel rows of W floats in LDS (32 KiB) */
+
+/* Backward of dmb_patch_match_step_f32 for the same L, R, noise_in, range and vertical.  With prob, s_j, n_j, T_j as there,
+ * gS = g_samples (the gradient of the samples: channels [gs_ch_offset, gs_ch_offset + P) of [B, gs_channels_total, H, W]),
+ * gN = g_noise (the gradient of noise_out, [B, P, H, W]); either may be NULL (= 0), not both; tc = temperature / C:
+ *   a_j   = gS * s_j + gN * n_j;  gc_j = prob_j * (a_j - sum_j prob_j * a_j)
+ *   dL[b, c, i] = dL_acc + tc * sum over p, j of gc_j * T_j[c]                 (ascending plane 3p + j: the same bits for any B)
+ *   dR          = dR_acc + the sampler's adjoint of tc * gc_j * L[b, c, i] on plane 3p + j: the forward's taps and weights,
+ *                 zero padding, half weight on the first and last plane (row sums in LDS in the hardware's order, then the
+ *                 partial rows of a source row in ascending y, as dmb_fast_fms_bwd_f32)
+ *   gs_j  = prob_j * gS + tc * gc_j * sum_c L[b, c, i] * dT_j[c] / ds,  dT / ds = the sampler's column derivative times
+ *           -W / (W - 1) as dmb_fast_fms_bwd_f32 takes it for d_samples; taps outside the image count 0
+ *   d_noise_in[b, p, i] = gn_1 at i + gn_0 at the next pixel + gn_2 at the previous one (along x, or y if vertical), in this
+ *           order, gn_j = prob_j * gN + (max - min) * (float)(1 / (P + 1)) * gs_j: the same bits from run to run and for any B
+ * The candidates, taps and costs are recomputed by the forward's own device functions (the cell floor(ix) of a candidate is the
+ * forward's).  The range maps are constants: they receive no gradient.  dL_acc, dR_acc: [B, C, H, W] or NULL (= 0); each may be
+ * the output it is added into.  dL, dR: [B, C, H, W]; d_noise_in: [B, P, H, W]; every element is written once.
+ * workspace: 6 * B * P * H * W + 2 * B * C * H * W floats (gc, gn, the partial rows), left undefined.
+ * The forward's range of sizes and W <= DMB_PATCH_MATCH_BWD_MAX_W: DMB_EUNSUPPORTED otherwise; operands 4-byte aligned. */
+int dmb_patch_match_step_bwd_f32(const float* L, const float* R, const float* noise_in, const float* min_disp,
+                                 const float* max_disp, float min_const, float max_const, const float* g_samples,
+                                 const float* g_noise, const float* dL_acc, const float* dR_acc, float* dL, float* dR,
+                                 float* d_noise_in, float* workspace, int B, int C, int P, int H, int W, int vertical,
+                                 float temperature, int gs_channels_total, int gs_ch_offset, void* stream);
+
+/* Backward of dmb_deeppruner_uniform_samples_f32: d_out [B, N, H, W] -> d_min, d_max [B, 1, H, W], every element written once.
+ * d min = sum_k d_out_k * (1 - f_k), d max = sum_k d_out_k * f_k, f_k = (float)k / (float)(N - 1), ascending k; range_head != 0:
+ * then through the clamps, the halving, the shortfall and the ordering of DeepPruner.py:48-66 with torch's subgradients
+ * (minimum / maximum split a tie in halves, clamp passes the gradient at its bounds).  min_disp, max_disp: the forward's inputs,
+ * read only when range_head != 0. */
+int dmb_deeppruner_uniform_samples_bwd_f32(const float* min_disp, const float* max_disp, const float* d_out, float* d_min,
+                                           float* d_max, int B, int H, int W, int N, int range_head, float max_disp_limit,
+                                           void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * DeepPruner's cost processor (cost_processors/DeepPruner.py), forward only: csrc/deeppruner_heads.hip
