@@ -27,6 +27,18 @@
  *     kernel-variant switches exist only in the development build (build.py dev=True ->
  *     lib/libdmb_hip_dev.so, used by scripts/, never by the package, the tests or bench.py).
  *
+ * Sizes:
+ *   - inside ONE batch item the kernels address memory with 32-bit byte offsets (hand-built buffer resources, LDS-DMA copies):
+ *     where an entry point says that an item -- or some channels of it -- stays "below 2 GiB", a larger one is refused with
+ *     DMB_EUNSUPPORTED before any launch;
+ *   - ACROSS batch items every base is 64-bit, so the size of an operand as a whole is limited only by the batch count: a tensor
+ *     may pass 2 GiB, 4 GiB and 2^31 elements as long as each item stays within the rule above.  Where the batch count is a grid
+ *     dimension -- most entry points -- B may be at most 65535 (dmb_cat_fms_bwd_f32 / dmb_dif_fms_bwd_f32: B * C); beyond that the
+ *     call returns DMB_EUNSUPPORTED or the launch's hipError_t, and nothing is computed;
+ *   - element and row counts (`rows`, `n`, `n_elements`, `S`) are `long long`.
+ *   Supported or refused, never silently wrong: tests/test_large_tensors_gpu.py launches the entry points on operands of more than
+ *   2^31 elements, the size coming from B alone, and compares every item with launches on slices below 2 GiB.
+ *
  * Each entry point names the reference interface it replaces (file:line under the reference
  * tree).  The reference is pure PyTorch on this path, so "replaces" means: the same
  * arithmetic that those torch calls perform, as one hand-written HIP kernel launch.
@@ -711,7 +723,8 @@ int dmb_channel_dot_f32(const float* a, const float* g, double* workspace, float
 int dmb_cat_first_wgrad_maps_f32(const float* dc, float* maps_left, float* maps_right, int B, int Co, int D, int H, int W, void* stream);
 
 /* Backward of the cost-volume builders: dvol [B, 2C (cat) or C (dif), D, H, W] -> dL, dR [B, C, H, W]; sums over the
- * valid columns of every disparity plane (cat_fms.py:36-44), FP32 in ascending plane order. */
+ * valid columns of every disparity plane (cat_fms.py:36-44), FP32 in ascending plane order.  B * C and 2 H are grid dimensions:
+ * at most 65535 each, DMB_EUNSUPPORTED beyond. */
 int dmb_cat_fms_bwd_f32(const float* dvol, float* dL, float* dR, int B, int C, int H, int W, int D,
                         const int* disp_idx_host, void* stream);
 int dmb_dif_fms_bwd_f32(const float* dvol, float* dL, float* dR, int B, int C, int H, int W, int D,
