@@ -207,23 +207,35 @@ __global__ __launch_bounds__(256, 1) void conv3d_wgrad_s1_kernel(const float* __
 // Staging units are linear in LDS across channels (the unit count per channel is made odd: pitch = 4 mod 8 floats), so one LDS-DMA
 // instruction moves 64 units whatever the plane size.
 // ------------------------------------------------------------------------------------------------------------------
+// Stride (1, 2, 2) (Db == Ds >= 2): out[cs, cb, kz, ky, kx] = sum small[b, cs, z, y, x] * big[b, cb, z + kz - 1, 2y + ky - 1,
+// 2x + kx - 1] is the same kernel on WgHwCfg (ZS = 1): the staged tile, the pitches and the fragment reads are those of stride 2
+// (the plane is strided the same way); only the ring (four slots, one landing) and the plane numbers of the walk differ.
 // (round 6) The tile is a parameter: 2 x 12 (84 MFMAs per wave between two barriers) or 4 x 8 (112; and 64-column rows -- the
 // training crops -- tile exactly where 12-column tiles compute 72); wgrad_plan picks per launch.
-template <int TY_, int TX_>
-struct Wg2Cfg {
-  static constexpr int TY = TY_, TX = TX_, ROWS = 2 * TY + 1, XOFF = 3;
+// ZS: the stride along z.  2 = the stride-2 units (Wg2Cfg).  1 = the units that stride only height and width (DeepPruner's
+// hourglass, stride (1, 2, 2): WgHwCfg): the plane of the tile is the same, the walk along z is the stride-1 kernel's -- a small plane
+// z needs big planes z - 1, z, z + 1: a ring of four slots with one landing per step.
+template <int TY_, int TX_, int ZS_>
+struct Wg2Tile {
+  static constexpr int TY = TY_, TX = TX_, ZS = ZS_, ROWS = 2 * TY + 1, XOFF = 3;
   static constexpr int P = (4 + 2 * TX + 3) / 4 * 4;            // staged row of the big tile: aligned column 2 x0 - 4 ..
   static constexpr int UBU = ROWS * P / 4, USU = TY * TX / 4;   // 16-byte units per channel plane ...
   static constexpr int UB = UBU | 1, US = USU | 1;              // ... padded to an odd count (pitch = 4 mod 8 floats)
   static constexpr int SB = UB * 4, SS = US * 4;                // channel pitches (floats)
   static constexpr int BPLANE = 32 * SB, SPLANE = 32 * SS;
-  static constexpr int NRING = 5;
+  static constexpr int NRING = 3 + ZS;                          // three big planes in use, ZS landing
   static constexpr int LDS_FLOATS = NRING * BPLANE + 2 * SPLANE;
   static constexpr int KSTEPS = TY * TX / 2;
   static constexpr int NTAPW = 7;
   static constexpr int IB = (32 * UB + 255) / 256, IS = (32 * US + 255) / 256;   // copy instructions per wave and plane
-  static_assert(SB % 8 == 4 && SS % 8 == 4 && LDS_FLOATS * 4 <= 160 * 1024 && 2 * IB + IS <= KSTEPS && TX % 4 == 0, "tile");
+  static_assert(SB % 8 == 4 && SS % 8 == 4 && LDS_FLOATS * 4 <= 160 * 1024 && ZS * IB + IS <= KSTEPS && TX % 4 == 0 && (ZS == 1 || ZS == 2), "tile");
 };
+
+template <int TY_, int TX_>
+struct Wg2Cfg : Wg2Tile<TY_, TX_, 2> {};
+// Stride (1, 2, 2) has ONE tile, 4 x 8: the training shapes (small planes of 8 x 16, 16 x 32 and 32 x 64) tile exactly, and a wave
+// issues 112 MFMAs between two barriers (2 x 12 would compute 24 columns for 16, 36 for 32, 72 for 64).
+struct WgHwCfg : Wg2Tile<4, 8, 1> {};
 
 template <class C, bool V16>
 __global__ __launch_bounds__(256, 1) void conv3d_wgrad_s2_kernel(const float* __restrict__ sm, const float* __restrict__ bg,
@@ -328,22 +340,22 @@ __global__ __launch_bounds__(256, 1) void conv3d_wgrad_s2_kernel(const float* __
         }
       }
     };
-    // ring slot of big plane p: (p - (2 za - 1)) % 5
+    // ring slot of big plane p: (p - (ZS za - 1)) % NRING
     __syncthreads();
     if constexpr (V16) {
 #pragma unroll
       for (int q = 0; q < 3; ++q)
 #pragma unroll
-        for (int j = 0; j < C::IB; ++j) stage_b1(2 * za - 1 + q, q, j);
+        for (int j = 0; j < C::IB; ++j) stage_b1(C::ZS * za - 1 + q, q, j);
 #pragma unroll
       for (int j = 0; j < C::IS; ++j) stage_s1(za, 0, j);
     } else {
-      for (int q = 0; q < 3; ++q) stage_b_rows(2 * za - 1 + q, q);
+      for (int q = 0; q < 3; ++q) stage_b_rows(C::ZS * za - 1 + q, q);
       stage_s_rows(za, 0);
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);
     __syncthreads();
-    int q0 = 0;   // ring index of plane 2 z - 1
+    int q0 = 0;   // ring index of plane ZS z - 1
     for (int z = za; z < zb; ++z) {
       const int rel = z - za;
       const bool more = z + 1 < zb;
@@ -353,9 +365,9 @@ __global__ __launch_bounds__(256, 1) void conv3d_wgrad_s2_kernel(const float* __
       for (int i = 0; i < C::NTAPW; ++i) bp[i] = ring + ((q0 + tapdz[i]) % C::NRING) * C::BPLANE + tapoff[i];
       const int s3 = (q0 + 3) % C::NRING, s4 = (q0 + 4) % C::NRING;
       if constexpr (!V16) {
-        if (more) {
-          stage_b_rows(2 * z + 2, s3);
-          stage_b_rows(2 * z + 3, s4);
+        if (more) {   // the planes the next step adds: ZS (z + 1) + 1 and, with a z stride, the one before it
+          stage_b_rows(C::ZS * z + 2, s3);
+          if constexpr (C::ZS == 2) stage_b_rows(2 * z + 3, s4);
           stage_s_rows(z + 1, (rel + 1) & 1);
         }
       }
@@ -375,15 +387,15 @@ __global__ __launch_bounds__(256, 1) void conv3d_wgrad_s2_kernel(const float* __
         for (int i = 0; i < C::NTAPW; ++i) acc[i] = DMB_MFMA(af[q & 1], bf[q & 1][i], acc[i]);
         if (V16 && more) {   // the next planes, one copy per k-step
           if (q < C::IB)
-            stage_b1(2 * z + 2, s3, q);
-          else if (q < 2 * C::IB)
+            stage_b1(C::ZS * z + 2, s3, q);
+          else if (C::ZS == 2 && q < 2 * C::IB)
             stage_b1(2 * z + 3, s4, q - C::IB);
-          else if (q < 2 * C::IB + C::IS)
-            stage_s1(z + 1, (rel + 1) & 1, q - 2 * C::IB);
+          else if (q >= C::ZS * C::IB && q < C::ZS * C::IB + C::IS)
+            stage_s1(z + 1, (rel + 1) & 1, q - C::ZS * C::IB);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
-      q0 = (q0 + 2) % C::NRING;
+      q0 = (q0 + C::ZS) % C::NRING;
       __builtin_amdgcn_s_waitcnt(0x0F70);
       __syncthreads();
     }
@@ -744,6 +756,7 @@ struct WgS2Form {
 };
 using WgS1Forms = std::tuple<WgS1Form<true, 24>, WgS1Form<true, 32>, WgS1Form<false, 24>>;
 using WgS2Forms = std::tuple<WgS2Form<Wg2Cfg<2, 12>, true>, WgS2Form<Wg2Cfg<2, 12>, false>, WgS2Form<Wg2Cfg<4, 8>, true>, WgS2Form<Wg2Cfg<4, 8>, false>>;
+using WgHwForms = std::tuple<WgS2Form<WgHwCfg, true>, WgS2Form<WgHwCfg, false>>;   // stride (1, 2, 2)
 using Wg2dForms = std::tuple<Wg2dCfg<3, 1>, Wg2dCfg<3, 2>, Wg2dCfg<3, 4>, Wg2dCfg<3, 8>, Wg2dCfg<1, 1>>;
 
 template <class L, class F, size_t... I>
@@ -816,11 +829,22 @@ int wgrad_plan(const WgradDesc& d, WgradPlan* p, const char** why) {
   if (d.kind == DMB_WGRAD_S2) {   // Co / D, H, W: the small operand's; Ci / Db, Hb, Wb: the big one's
     const int Db = d.Db, Hb = d.Hb, Wb = d.Wb;
     if (B <= 0 || Co <= 0 || Ci <= 0 || D <= 0 || H <= 0 || W <= 0) return refuse(DMB_EINVAL, "conv3d_s2_wgrad: bad argument");
-    if ((Db != 2 * D && Db != 2 * D - 1) || (Hb != 2 * H && Hb != 2 * H - 1) || (Wb != 2 * W && Wb != 2 * W - 1))
+    // only height and width strided (stride (1, 2, 2)): the same depth, two planes or more.  (One plane of either reading is the
+    // same sum and stays on the stride-2 kernels.)
+    const bool hw = Db == D && D >= 2;
+    if ((!hw && Db != 2 * D && Db != 2 * D - 1) || (Hb != 2 * H && Hb != 2 * H - 1) || (Wb != 2 * W && Wb != 2 * W - 1))
       return refuse(DMB_EINVAL, "conv3d_s2_wgrad: the big tensor must be 2n or 2n - 1 per axis");
     if ((long long)32 * Db * Hb * Wb * 4 >= LIM) return refuse(DMB_EUNSUPPORTED, "conv3d_s2_wgrad: 32 channels of one batch item must stay below 2 GiB");
     const bool v16 = W % 4 == 0 && Wb % 4 == 0 && aligned;
     const int nslots = wgrad_slots_per_block(Co, Ci, 1, ncu);
+    if (hw) {   // one tile; the segments are what fills the CUs from the few tiles of these layers
+      typedef std::tuple_element_t<0, WgHwForms>::C C;
+      const int ntx = cdiv(W, C::TX), nty = cdiv(H, C::TY);
+      const long long per_seg = (long long)B * ntx * nty;
+      int zseg = segment_search(D, per_seg, nslots, WG_SEG_HW);
+      if (DMB_OPT(5) > 0) zseg = cdiv(D, DMB_OPT(5));   // (development option 5: number of z segments)
+      return planned(WGRAD_HW, v16 ? 0 : 1, ntx, nty, D, zseg, per_seg, nslots);
+    }
     // z segments and the launch's cost for a tile shape: rounds of items on the slots x (planes per item + prologue) x the tile's
     // k-steps, over what the tile reaches between its barriers (4 x 8: 112 MFMAs per wave and barrier against 84; measured at the
     // training crop, profiles/r06_wgrad_s2_tiles.log)
@@ -908,12 +932,13 @@ extern "C" int dmb_conv3d_k3s2_wgrad_f32(const float* small, const float* big, f
   int rc = wgrad_plan({DMB_WGRAD_S2, B, Cs, Cb, Ds, Hs, Ws, Db, Hb, Wb, 3, 1, align_of_both(small, big), num_cus()}, &p, &why);
   if (rc != DMB_OK) return fail(rc, why);
   hipStream_t st = (hipStream_t)stream;
-  rc = wg_visit<WgS2Forms>(p.code, [&](auto f) {
+  auto run = [&](auto f) {
     typedef decltype(f) F;
     static unsigned long long seen = 0;
     return wg_launch(&conv3d_wgrad_s2_kernel<typename F::C, F::V16>, F::C::LDS_FLOATS * 4, &seen, p, st, "conv3d_s2_wgrad launch failed", small, big,
                      workspace, B, Cs, Cb, Ds, Hs, Ws, Db, Hb, Wb, p.ntx, p.nty, p.nseg, p.seg);
-  });
+  };
+  rc = p.code >> 8 == WGRAD_HW ? wg_visit<WgHwForms>(p.code, run) : wg_visit<WgS2Forms>(p.code, run);
   if (rc != DMB_OK) return rc;
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(p.blocks * 27 * 16), dim3(256), 0, st, workspace, dw, Cs, Cb, p.slots);
   return launch_status("conv3d_s2_wgrad reduce launch failed");

@@ -13,11 +13,12 @@
 
 namespace dmb {
 // the form, bits 8.. of a plan code; bits 0-7: the position in the form's list of instantiations (wgrad.hip)
-enum { WGRAD_S1 = 1, WGRAD_S2 = 2, WGRAD_C1 = 3, WGRAD_2D = 4 };
+enum { WGRAD_S1 = 1, WGRAD_S2 = 2, WGRAD_C1 = 3, WGRAD_2D = 4, WGRAD_HW = 5 };
 
 // What the three entry points decide a launch from: no pointers, no device.
 struct WgradDesc {
-  int kind;             // DMB_WGRAD_S1 (plans WGRAD_S1, or WGRAD_C1 for one output channel), DMB_WGRAD_S2, DMB_WGRAD_2D
+  int kind;             // DMB_WGRAD_S1 (plans WGRAD_S1, or WGRAD_C1 for one output channel), DMB_WGRAD_S2 (WGRAD_S2, or WGRAD_HW
+                        // where the operands have the same depth of two planes or more), DMB_WGRAD_2D
   int B, Co, Ci;        // channels of the operand that gives dw its rows (dc; stride 2: small) and its columns (x; stride 2: big)
   int D, H, W;          // extents of both operands; stride 2: of the small one; 2-D: D = 1
   int Db, Hb, Wb;       // stride 2: extents of the big operand
@@ -41,6 +42,10 @@ struct WgSeg {
   double prologue;   // what starting a segment costs, in planes: the ring is filled before the first multiply
 };
 constexpr WgSeg WG_SEG_S1 = {4, 0.5}, WG_SEG_S2 = {4, 1.0}, WG_SEG_2D = {8, 2.0};
+// Stride (1, 2, 2): the layers are small (8 x 16 to 32 x 64 planes, 9 or 14 deep), so a segment may be a single plane, and a segment's
+// start -- three big planes and one small one staged with nothing to multiply -- costs about one plane's step (fitted on the
+// 128 <- 64 launch at [1, 128, 9, 8, 16]: docs/design/20-deeppruner-aggregator-backward.md)
+constexpr WgSeg WG_SEG_HW = {1, 1.0};
 constexpr double WG2_EFF_4x8 = 1.1;   // rate of the 4 x 8 stride-2 tile relative to 2 x 12 on shapes both tile exactly (wgrad_plan)
 
 inline int segment_search(int extent, long long items_per_segment_count, int nslots, WgSeg s, double* cost_out = nullptr) {

@@ -180,6 +180,8 @@ def _conv_raw(unit, x, wpack, bias):
     Co = unit.out_planes
     scale, shift = _bias_as_shift(bias)
     if unit.transposed:
+        if unit.stride == unit.HW:
+            return ops.deconv3d_k3s2(x, wpack, Co, scale, shift, None, False, stride=unit.HW)
         return ops.deconv3d_k3s2(x, wpack, Co, scale, shift, None, False)
     return ops.conv3d_k3(x, wpack, Co, scale, shift, None, unit.stride, False)
 
@@ -360,13 +362,13 @@ class ConvUnitFn(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             if unit.transposed:
                 dw = ops.deconv3d_k3s2_wgrad(x, dc)
-            elif unit.stride == 2:
+            elif unit.stride in (2, unit.HW):     # (the library reads which of the two from the operands' depths)
                 dw = ops.conv3d_k3s2_wgrad(x, dc)
             else:
                 dw = ops.conv3d_k3_wgrad(x, dc)
         if ctx.needs_input_grad[0]:
             wp = ctx.wp_bwd if w._version == ctx.w_version else None
-            dx = (ops.deconv3d_k3s2_dgrad(dc, w, residual=dx_acc, wpack=wp) if unit.transposed
+            dx = (ops.deconv3d_k3s2_dgrad(dc, w, residual=dx_acc, wpack=wp, stride=unit.stride) if unit.transposed
                   else ops.conv3d_k3_dgrad(dc, w, unit.stride, tuple(x.shape[2:]), residual=dx_acc, wpack=wp))
         return _unit_backward_tail(ctx, dx, dw, bn_grads)
 
@@ -964,6 +966,69 @@ def deeppruner_sampler(sampler, stage, left, right, min_disparity=None, max_disp
     _refuse_cpu("deeppruner_sampler", min_disparity, max_disparity)
     return UniformSamplesFn.apply(min_disparity.contiguous(), max_disparity.contiguous(),
                                   sampler.uniform_sampler.disparity_sample_number, sampler.max_disp)
+
+
+# ---------------------------------------------------------------------------------------------- DeepPruner's aggregator
+class _SingleBackwardFn(torch.autograd.Function):
+    """Identity on the output of a function built from the units above.  Its backward runs before any of theirs, so a double
+    backward is refused before the first launch."""
+
+    @staticmethod
+    def forward(ctx, y, what):
+        ctx.what = what
+        return y.view_as(y)
+
+    @staticmethod
+    def backward(ctx, dy):
+        _refuse_double_backward(ctx.what)
+        return dy, None
+
+
+def _hw_hourglass_units(hourglass, x, skip):
+    levels = []
+    for k in (1, 2, 3):                                   # down (hw_hourglass.py:79-94): relu(bn(conv)) + its own input
+        down = conv_unit(getattr(hourglass, "conv%d_a" % k), x, None, True)
+        x = conv_unit(getattr(hourglass, "conv%d_b" % k), down, down, "pre")
+        levels.append(x)
+    for k in (3, 2):                                      # up (:97-100): bn(deconv) + the level above, no ReLU
+        x = conv_unit(getattr(hourglass, "conv%d_d" % k), x, levels[k - 2], False)
+    return conv_unit(hourglass.conv1_d, x, skip, False)   # :103 (+ the caller's skip)
+
+
+def _check_hw_volume(what, x, planes):
+    if x.dim() != 5 or x.shape[1] != planes or x.shape[3] % 8 or x.shape[4] % 8:
+        raise ValueError("%s: input must be [B, %d, D, H, W] with H and W multiples of 8, got %s" % (what, planes, tuple(x.shape)))
+
+
+def hw_hourglass(hourglass, x, skip=None):
+    """Differentiable forward of an HWHourglass (whose own ``forward`` stays inference only): the nine units in the order and with
+    the adds of HWHourglass.forward, each on ConvUnitFn -- the stride-(1, 2, 2) ones with the (1, 2, 2) kernels of the other
+    direction as their data gradients and the (1, 2, 2) weight gradient (csrc/wgrad.hip).  ``skip``: the caller's
+    ``hourglass(x) + x``, added by conv1_d.  Every BatchNorm follows its own ``training`` flag."""
+    _check_hw_volume("HWHourglass", x, hourglass.in_planes)
+    if skip is not None and tuple(skip.shape) != tuple(x.shape):
+        raise ValueError("HWHourglass: skip shape %s != input shape %s" % (tuple(skip.shape), tuple(x.shape)))
+    _refuse_cpu("hw_hourglass", x, skip)
+    with carry_scope():
+        return _SingleBackwardFn.apply(_hw_hourglass_units(hourglass, x, skip), "hw_hourglass")
+
+
+def deeppruner_aggregator(aggregator, raw_cost):
+    """Differentiable forward of a DeepPrunerAggregator (whose own ``forward`` stays inference only): dres0, dres1, the hourglass
+    plus its input, the classifier (DeepPruner.py:47-59).  Returns ``[cost]``, [B, D, H, W]."""
+    if hasattr(raw_cost, "materialize"):
+        raw_cost = raw_cost.materialize()
+    _check_hw_volume("DeepPrunerAggregator", raw_cost, aggregator.in_planes)
+    _refuse_cpu("deeppruner_aggregator", raw_cost)
+    with carry_scope():
+        x = raw_cost
+        for unit in tuple(aggregator.dres0) + tuple(aggregator.dres1):            # DeepPruner.py:49-51
+            x = conv_unit(unit, x, None, True)
+        x = _hw_hourglass_units(aggregator.dres2, x, x)                           # :54, the add in conv1_d
+        x = conv_unit(aggregator.classify[0], x, None, True)
+        head = aggregator.classify[1]
+        cost = HeadConvFn.apply(x, head.weight, head.bias, None)                  # :57
+        return [_SingleBackwardFn.apply(cost, "deeppruner_aggregator").squeeze(1)]
 
 
 def wants_grad(module, *tensors):

@@ -790,7 +790,9 @@ def unit_pack_jobs(w, transposed, stride):
     gradient] (the table the reference's autograd hides in cuDNN: basic_layers.py:68-100,160-177 under train()).
       stride-1 Conv3d    [Co, Ci]: forward conv Ci -> Co; data gradient = conv Co -> Ci on mirrored taps
       stride-2 Conv3d    [Co, Ci]: forward conv; data gradient = the transposed convolution with the same tensor ([Ci_t, Co_t] = [Co, Ci])
-      ConvTranspose3d    [Ci, Co]: forward transposed; data gradient = stride-2 conv reading the tensor as [Co', Ci'] = [Ci, Co]"""
+      ConvTranspose3d    [Ci, Co]: forward transposed; data gradient = stride-2 conv reading the tensor as [Co', Ci'] = [Ci, Co]
+    A tuple stride -- (1, 2, 2), the units that stride only height and width -- takes the stride-2 rows: the (1, 2, 2) kernels read
+    the same two packed streams (csrc/conv3d_hw.hip), so the jobs, and the buffers _PackGroup sizes from them, are the same."""
     a, b = int(w.shape[0]), int(w.shape[1])
     if transposed:
         return [(b, a, PACK_DECONV), (a, b, PACK_CONV)]
@@ -826,8 +828,26 @@ def conv3d_k3_dgrad(dc, w, stride=1, in_size=None, residual=None, wpack=None):
     ``in_size`` = (D, H, W) of that input; needed for stride 2 when an extent is odd (the adjoint is computed for the even
     size 2 x output and its last plane / row / column dropped).  ``residual``: a tensor of the input's shape added to the result
     in the kernel's epilogue (the gradient the input already holds from its other consumers: train_fn's gradient carry).
-    ``wpack``: the data gradient's packed weights when the caller already holds them (unit_pack_jobs)."""
+    ``wpack``: the data gradient's packed weights when the caller already holds them (unit_pack_jobs).
+    ``stride`` (1, 2, 2): the transposed (1, 2, 2) kernel on the same weight tensor, 16, 32 or 64 input channels; an odd H or W of
+    ``in_size`` as for stride 2."""
     Co, Ci = w.shape[0], w.shape[1]
+    stride = _hw_stride(stride, "conv3d_k3_dgrad")
+    if stride == "hw":
+        if Ci not in _HW_DGRAD_CONV_CHANNELS:
+            raise _lib.DmbLibraryError("conv3d_k3_dgrad: stride (1, 2, 2) takes a layer of %s input channels, got %d"
+                                       % (" | ".join(str(c) for c in _HW_DGRAD_CONV_CHANNELS), Ci))
+        full = (dc.shape[2], 2 * dc.shape[3], 2 * dc.shape[4])
+        if in_size is not None and (in_size[0] != full[0] or any(a not in (b, b - 1) for a, b in zip(in_size[1:], full[1:]))):
+            raise _lib.DmbLibraryError("conv3d_k3_dgrad: input size %s does not belong to output size %s" % (tuple(in_size), tuple(dc.shape[2:])))
+        fused = residual is not None and (in_size is None or tuple(in_size) == full)
+        dx = deconv3d_k3s2(dc, wpack if wpack is not None else pack_deconv3d_weights(w), Ci, residual=residual if fused else None,
+                           stride=(1, 2, 2))
+        if in_size is not None and tuple(in_size) != full:
+            dx = dx[:, :, :, :in_size[1], :in_size[2]].contiguous()
+        if residual is not None and not fused:
+            dx = dx + residual
+        return dx
     if stride == 1:
         if Ci not in _CONV_OUT_CHANNELS:
             return _conv3d_k3_any_co(dc, Ci, 1, residual, lambda c0, n, npad: pack_conv3d_dgrad_weights(
@@ -855,13 +875,22 @@ def conv3d_k3_dgrad(dc, w, stride=1, in_size=None, residual=None, wpack=None):
         if residual is not None and not fused:
             dx = dx + residual
         return dx
-    raise _lib.DmbLibraryError("conv3d_k3_dgrad: stride must be 1 or 2")
+    raise _lib.DmbLibraryError("conv3d_k3_dgrad: stride must be 1, 2 or (1, 2, 2)")
 
 
-def deconv3d_k3s2_dgrad(dy, w, residual=None, wpack=None):
+def deconv3d_k3s2_dgrad(dy, w, residual=None, wpack=None, stride=2):
     """Gradient of nn.ConvTranspose3d(k=3, s=2, p=1, output_padding=1) w.r.t. its input; w is [Ci, Co, 3, 3, 3].  ``residual`` and
-    ``wpack`` as in conv3d_k3_dgrad."""
+    ``wpack`` as in conv3d_k3_dgrad.  ``stride`` (1, 2, 2): of the layer with output_padding (0, 1, 1) -- the (1, 2, 2) convolution on
+    the same weight tensor, 32, 64 or 128 input channels."""
     Ci = w.shape[0]
+    stride = _hw_stride(stride, "deconv3d_k3s2_dgrad")
+    if stride == "hw":
+        if Ci not in _CONV_OUT_CHANNELS:
+            raise _lib.DmbLibraryError("deconv3d_k3s2_dgrad: stride (1, 2, 2) takes a layer of %s input channels, got %d"
+                                       % (" | ".join(str(c) for c in _CONV_OUT_CHANNELS), Ci))
+        return conv3d_k3(dy, wpack if wpack is not None else pack_conv3d_weights(w), Ci, residual=residual, stride=(1, 2, 2))
+    if stride != 2:
+        raise _lib.DmbLibraryError("deconv3d_k3s2_dgrad: stride must be 2 or (1, 2, 2)")
     if Ci not in _CONV_OUT_CHANNELS:
         return _conv3d_k3_any_co(dy, Ci, 2, residual, lambda c0, n, npad: pack_conv3d_weights(
             torch.nn.functional.pad(w[c0:c0 + n], (0, 0, 0, 0, 0, 0, 0, 0, 0, npad - n))))
@@ -871,6 +900,7 @@ def deconv3d_k3s2_dgrad(dy, w, residual=None, wpack=None):
 # Output channel counts dmb_conv3d_k3_f32 takes (stride 1 and 2).  A data gradient is a forward launch whose output channels are the
 # layer's INPUT channels, which may be any count: those run as launches of 128 / 64 / 32 channels, the last on zero-padded weights.
 _CONV_OUT_CHANNELS = (32, 64, 128)
+_HW_DGRAD_CONV_CHANNELS = (16, 32, 64)   # output channels of the transposed (1, 2, 2) kernel: the hourglass's down layers' inputs
 
 
 def _conv3d_k3_any_co(x, Co, stride, residual, pack_rows):
@@ -915,12 +945,14 @@ def _s2_wgrad(small, big, what):
 
 
 def conv3d_k3s2_wgrad(x, dc):
-    """Weight gradient of nn.Conv3d(k=3, stride=2, padding=1): [Co, Ci, 3, 3, 3]."""
+    """Weight gradient of nn.Conv3d(k=3, stride=2, padding=1): [Co, Ci, 3, 3, 3].  Operands of the same depth (two planes or more)
+    are those of stride (1, 2, 2): the library reads the geometry from the two shapes."""
     return _s2_wgrad(dc, x, "dmb_conv3d_k3s2_wgrad_f32 (conv)")
 
 
 def deconv3d_k3s2_wgrad(x, dy):
-    """Weight gradient of nn.ConvTranspose3d(k=3, s=2, p=1, output_padding=1): [Ci, Co, 3, 3, 3]."""
+    """Weight gradient of nn.ConvTranspose3d(k=3, s=2, p=1, output_padding=1): [Ci, Co, 3, 3, 3]; of stride (1, 2, 2) with
+    output_padding (0, 1, 1) where x and dy have the same depth (two planes or more)."""
     return _s2_wgrad(x, dy, "dmb_conv3d_k3s2_wgrad_f32 (transposed conv)")
 
 

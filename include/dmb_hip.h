@@ -628,6 +628,11 @@ int dmb_conv3d_k3_wgrad_f32(const float* x, const float* dc, float* dw, float* w
  *   nn.Conv3d(k 3, s 2, p 1):                 small = dc [B, Co, Ds, Hs, Ws], big = x  [B, Ci, Db, Hb, Wb] -> dW [Co, Ci, 27]
  *   nn.ConvTranspose3d(k 3, s 2, p 1, op 1):  small = x  [B, Ci, ...],        big = dy [B, Co, 2Ds, ...]  -> dW [Ci, Co, 27]
  * Each big extent is 2n or 2n - 1 (16-byte staging when both widths are multiples of 4 and the tensors aligned).
+ * Db == Ds with Ds >= 2 selects the units that stride only height and width, out[cs, cb, kz, ky, kx] = sum_{b, z, y, x}
+ * small[b, cs, z, y, x] * big[b, cb, z + kz - 1, 2y + ky - 1, 2x + kx - 1] (Hb, Wb: 2n or 2n - 1 as above):
+ *   nn.Conv3d(k 3, s (1, 2, 2), p 1):                          small = dc, big = x  -> dW [Co, Ci, 27]
+ *   nn.ConvTranspose3d(k 3, s (1, 2, 2), p 1, op (0, 1, 1)):   small = x,  big = dy -> dW [Ci, Co, 27]
+ * (Ds == Db == 1 is the same sum in either reading.)  32 channels of one batch item of the big operand must stay below 2 GiB.
  * workspace: dmb_conv3d_wgrad_workspace_floats(Cs, Cb) floats. */
 int dmb_conv3d_k3s2_wgrad_f32(const float* small, const float* big, float* dw, float* workspace, int B, int Cs, int Cb,
                               int Ds, int Hs, int Ws, int Db, int Hb, int Wb, void* stream);
@@ -654,6 +659,8 @@ int dmb_conv2d_wgrad_f32(const float* x, const float* dc, float* dw, float* work
  *           x (planes per segment + 1) x tile voxels / 1.1 -- is below that of 2 x 12
  *   form 3  stride 1 with ONE output channel (Co == 1):  0
  *   form 4  2-D, strips of 64 columns walked along y:  0 .. 3 = kernel 3 with dilation 1, 2, 4, 8;  4 = kernel 1
+ *   form 5  DMB_WGRAD_S2 with Db == D >= 2 (stride (1, 2, 2)), tiles of 4 x 8 voxels of the small operand walked along z in segments of
+ *           one plane or more:  0 / 1 = 16-byte / dword staging (dword: either width % 4 != 0 or align < 16)
  * or -DMB_EINVAL / -DMB_EUNSUPPORTED where the launch would be refused with that code (dmb_last_error() then names the reason).
  * detail_host: NULL, or 6 host ints that receive the rest of the plan: tiles along x, tiles along y (2-D: the row classes = the dilation),
  * planes (2-D: rows of a class) per segment, segments (form 3: 1 and D), workgroup slots per channel block (grid x; form 3: the
