@@ -514,13 +514,14 @@ __global__ __launch_bounds__(256, 4) void conv3d_c1_wgrad_kernel(const float* __
   }
 }
 
-// One wave per (channel, tap): the lanes walk the workgroups' partials 64 apart (independent loads; one thread walking all of
+// One wave per number of the result ((channel, tap)): the lanes walk the workgroups' partials 64 apart (independent loads; one thread walking all of
 // them alone was a chain of 256 .. 1024 dependent-latency loads, 63 us for 864 numbers), each in FP64, then a fixed butterfly.
-__global__ __launch_bounds__(256) void conv3d_c1_wgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw, int Ci, int nchunk) {
+// (n = Ci x 27 numbers per workgroup; the 5x5 form below: Co x Ci x 25 per slot)
+__global__ __launch_bounds__(256) void wgrad_reduce_flat_kernel(const float* __restrict__ ws, float* __restrict__ dw, int n, int nchunk) {
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (i >= Ci * 27) return;
+  if (i >= n) return;
   double s = 0.0;
-  for (int c = lane; c < nchunk; c += 64) s += (double)ws[(size_t)c * Ci * 27 + i];
+  for (int c = lane; c < nchunk; c += 64) s += (double)ws[(size_t)c * n + i];
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
   if (lane == 0) dw[i] = (float)s;
@@ -741,6 +742,113 @@ __global__ void conv2d_wgrad_reduce_kernel(const float* __restrict__ ws, float* 
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// 2-D, kernel 5 on 1 .. DMB_CONV2D_K5_MAX_C channels (plan form 6): dW[co, ci, ky, kx] = sum_{b, y, x} dc[b, co, y, x] *
+// x[b, ci, y + ky - 2, x + kx - 2] for nn.Conv2d(k 5, s 1, p 2) -- DeepPruner's range heads and its disparity refinement tail
+// (SmallConv5x5).  M = Co <= 16 and N = Ci x 25 <= 400 against K = B x H x W: a 32 x 32 MFMA tile would be three quarters zeros at
+// 14 -> 14 and all but one row at 1 -> 1, so this is a VALU kernel.  A workgroup walks tiles of 8 rows x 32 columns: the haloed x
+// tile (12 x 36 per channel) and the dc tile go to LDS with plain loads (any width, any alignment, zeros outside the image); a
+// thread owns ONE (co, ci) pair and its 25 taps in registers for the whole launch, and per tile row reads the dc row (32 floats)
+// and five x rows (36 floats each) into registers: 212 LDS reads per 800 FMAs.  Where Co x Ci <= 128 the tile's rows are dealt
+// out to 256 / (Co x Ci) groups of threads (at most 8), added in ascending group order through LDS at the end.  Channel pitches
+// are odd: the lanes of a wave differ in ci (and read the same dc word).  Partial results per slot [Co][Ci][25] go to the workspace
+// and are added over the slots in FP64 in a fixed order: no atomics, bit-reproducible.
+// ------------------------------------------------------------------------------------------------------------------
+struct Wg5Cfg {
+  static constexpr int MAXC = DMB_CONV2D_K5_MAX_C, KS = 5, NTAP = KS * KS, HALO = KS / 2;
+  static constexpr int TY = 8, TX = 32;
+  static constexpr int XR = TY + 2 * HALO, XP = TX + 2 * HALO;   // rows and row pitch of the haloed x tile
+  static constexpr int XC = XR * XP + 1, DC = TY * TX + 1;       // channel pitches (floats), odd
+  static constexpr int PER_CU = 2;
+  // row groups of a launch, and its LDS: the two tiles, or the groups' partial results at the end
+  static constexpr int groups(int Co, int Ci) { return 256 / (Co * Ci) < TY ? 256 / (Co * Ci) : TY; }
+  static constexpr int lds_floats(int Co, int Ci) {
+    const int tiles = Ci * XC + Co * DC, red = groups(Co, Ci) * Co * Ci * NTAP;
+    return tiles > red ? tiles : red;
+  }
+  static_assert(MAXC * MAXC <= 256 && MAXC * MAXC * NTAP <= 9 * 1024, "one thread per pair; a slot's partial result fits the 2-D workspace");
+  static_assert(MAXC * (XC + DC) * 4 * PER_CU <= 160 * 1024 && 256 * NTAP * 4 * PER_CU <= 160 * 1024, "tile");
+};
+
+// An item = (batch item, tile row, tile column); nty tile rows.  workspace: ws[slot][co][ci][tap]
+__global__ __launch_bounds__(256, Wg5Cfg::PER_CU) void conv2d_k5_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dc,
+                                                                             float* __restrict__ ws, int B, int Ci, int Co, int H, int W,
+                                                                             int ntx, int nty) {
+  typedef Wg5Cfg C;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* xs = lds;
+  float* ds = lds + Ci * C::XC;
+  const int slot = xcd_remap(blockIdx.x, gridDim.x), nslots = gridDim.x;
+  const int tid = threadIdx.x;
+  const int np = Co * Ci, G = C::groups(Co, Ci);
+  const bool active = tid < G * np;
+  const int pair = tid % np, grp = tid / np;
+  const int co = pair / Ci, ci = pair - co * Ci;
+  const size_t HW = (size_t)H * W;
+  const int items = B * nty * ntx;
+
+  float acc[C::NTAP];
+#pragma unroll
+  for (int t = 0; t < C::NTAP; ++t) acc[t] = 0.f;
+
+  for (int it = slot; it < items; it += nslots) {
+    const int tx = it % ntx;
+    const int r = it / ntx;
+    const int ty = r % nty, b = r / nty;
+    const int x0 = tx * C::TX, y0 = ty * C::TY;
+    const float* xb = x + (size_t)b * Ci * HW;
+    const float* db = dc + (size_t)b * Co * HW;
+    __syncthreads();   // the previous tile is still being read by slower waves
+    for (int i = tid; i < Ci * C::XR * C::XP; i += 256) {
+      const int ch = i / (C::XR * C::XP), q = i - ch * (C::XR * C::XP);
+      const int row = q / C::XP, col = q - row * C::XP;
+      const int gy = y0 - C::HALO + row, gx = x0 - C::HALO + col;
+      xs[ch * C::XC + row * C::XP + col] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? xb[ch * HW + (size_t)gy * W + gx] : 0.f;
+    }
+    for (int i = tid; i < Co * C::TY * C::TX; i += 256) {
+      const int ch = i / (C::TY * C::TX), q = i - ch * (C::TY * C::TX);
+      const int row = q / C::TX, col = q - row * C::TX;
+      const int gy = y0 + row, gx = x0 + col;
+      ds[ch * C::DC + row * C::TX + col] = (gy < H && gx < W) ? db[ch * HW + (size_t)gy * W + gx] : 0.f;
+    }
+    __syncthreads();
+    if (active) {
+      const int rows = min(C::TY, H - y0);   // (rows past the image hold zeros of dc)
+      for (int row = grp; row < rows; row += G) {
+        float dr[C::TX];
+        const float* dp = ds + co * C::DC + row * C::TX;
+#pragma unroll
+        for (int j = 0; j < C::TX; ++j) dr[j] = dp[j];
+#pragma unroll
+        for (int ky = 0; ky < C::KS; ++ky) {
+          float xr[C::XP];
+          const float* xp = xs + ci * C::XC + (row + ky) * C::XP;
+#pragma unroll
+          for (int j = 0; j < C::XP; ++j) xr[j] = xp[j];
+#pragma unroll
+          for (int j = 0; j < C::TX; ++j)
+#pragma unroll
+            for (int kx = 0; kx < C::KS; ++kx) acc[ky * C::KS + kx] = fmaf(dr[j], xr[j + kx], acc[ky * C::KS + kx]);
+        }
+      }
+    }
+  }
+  // the row groups' results, added in ascending group order (the tiles' LDS is free now)
+  __syncthreads();
+  float* red = lds;
+  if (active) {
+#pragma unroll
+    for (int t = 0; t < C::NTAP; ++t) red[(grp * np + pair) * C::NTAP + t] = acc[t];
+  }
+  __syncthreads();
+  float* wsb = ws + (size_t)slot * np * C::NTAP;
+  for (int e = tid; e < np * C::NTAP; e += 256) {
+    float s = red[e];
+    for (int g = 1; g < G; ++g) s += red[g * np * C::NTAP + e];
+    wsb[e] = s;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // The instantiations a launch can run: ONE list per form.  Bits 0-7 of a plan code are the position in the form's list
 // (include/dmb_hip.h numbers them); wgrad_plan names a position and wg_visit is the only place where one becomes a type.
 // ------------------------------------------------------------------------------------------------------------------
@@ -863,6 +971,13 @@ int wgrad_plan(const WgradDesc& d, WgradPlan* p, const char** why) {
   if (d.kind == DMB_WGRAD_2D) {
     if (B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0) return refuse(DMB_EINVAL, "conv2d_wgrad: bad argument");
     if ((long long)32 * H * W * 4 >= LIM) return refuse(DMB_EUNSUPPORTED, "conv2d_wgrad: 32 channels of one image must stay below 2 GiB");
+    if (d.ksize == 5 && d.dilation == 1 && Co <= Wg5Cfg::MAXC && Ci <= Wg5Cfg::MAXC) {   // small-channel 5x5: any width, any alignment
+      typedef Wg5Cfg C;
+      const int ntx = cdiv(W, C::TX);
+      if ((long long)B * ntx * cdiv(H, C::TY) > LIM) return refuse(DMB_EUNSUPPORTED, "conv2d_wgrad (kernel 5): too many tiles");
+      // one row class; a "segment" is a tile's rows: items = B x tiles, accumulated in registers by the slot that walks them
+      return planned(WGRAD_K5, 0, ntx, 1, H, C::TY, (long long)B * ntx, wgrad_slots_per_block(Co, Ci, C::PER_CU, ncu));
+    }
     if (W % 4 != 0 || !aligned) return refuse(DMB_EUNSUPPORTED, "conv2d_wgrad: the width must be a multiple of 4 and the tensors 16-byte aligned");
     const int dil = d.ksize == 1 ? 1 : d.dilation;   // (a 1x1 layer has no dilation)
     const int index = d.ksize == 1 ? 4 : (d.ksize != 3 ? -1 : (dil == 1 ? 0 : (dil == 2 ? 1 : (dil == 4 ? 2 : (dil == 8 ? 3 : -1)))));
@@ -910,7 +1025,7 @@ extern "C" int dmb_conv3d_k3_wgrad_f32(const float* x, const float* dc, float* d
   if (p.code >> 8 == WGRAD_C1) {
     hipLaunchKernelGGL(conv3d_c1_wgrad_kernel, dim3((unsigned)p.slots, (unsigned)p.blocks), dim3(256), 0, st, x, dc, workspace, B, Ci, D, H, W, p.ntx,
                        p.nty, B * p.nseg * p.ntx * p.nty);
-    hipLaunchKernelGGL(conv3d_c1_wgrad_reduce_kernel, dim3(cdiv(Ci * 27, 4)), dim3(256), 0, st, workspace, dw, Ci, p.slots);
+    hipLaunchKernelGGL(wgrad_reduce_flat_kernel, dim3(cdiv(Ci * 27, 4)), dim3(256), 0, st, workspace, dw, Ci * 27, p.slots);
     return launch_status("conv3d_wgrad (1 channel) launch failed");
   }
   rc = wg_visit<WgS1Forms>(p.code, [&](auto f) {
@@ -952,6 +1067,13 @@ extern "C" int dmb_conv2d_wgrad_f32(const float* x, const float* dc, float* dw, 
   const int rc = wgrad_plan({DMB_WGRAD_2D, B, Co, Ci, 1, H, W, 0, 0, 0, ksize, dilation, align_of_both(x, dc), num_cus()}, &p, &why);
   if (rc != DMB_OK) return fail(rc, why);
   hipStream_t st = (hipStream_t)stream;
+  if (p.code >> 8 == WGRAD_K5) {
+    hipLaunchKernelGGL(conv2d_k5_wgrad_kernel, dim3((unsigned)p.slots), dim3(256), Wg5Cfg::lds_floats(Co, Ci) * 4, st, x, dc, workspace, B, Ci, Co, H, W,
+                       p.ntx, p.nseg);
+    const int n = Co * Ci * Wg5Cfg::NTAP;
+    hipLaunchKernelGGL(wgrad_reduce_flat_kernel, dim3(cdiv(n, 4)), dim3(256), 0, st, workspace, dw, n, p.slots);
+    return launch_status("conv2d_wgrad (kernel 5) launch failed");
+  }
   return wg_visit<Wg2dForms>(p.code, [&](auto c) {
     typedef decltype(c) C;
     static unsigned long long seen = 0;

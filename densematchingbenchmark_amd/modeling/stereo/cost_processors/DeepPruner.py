@@ -6,7 +6,14 @@ Launches.  The raw volume of both stages is ONE launch of csrc/deeppruner_heads.
 sampled concatenation volume, the samples and -- stage "post" -- the range features on every plane, each element written once).
 The 3-D layers are the fused units of the aggregator (layers/basic_layers.py, utils/hw_hourglass.py), the 32 -> 1 ends
 ``HeadConv3d``, the regressions ``ops.soft_argmin_sampled``, the up-sampling ``ops.bilinear_scale`` and the six 5x5 convolutions
-``SmallConv5x5``.  Stage "pre": 1 + 4 + 2 * 11 + 2 + 4 = 33 launches; stage "post": 1 + 14 + 1 + 2 + 2 = 20.  Inference only."""
+``SmallConv5x5``.  Stage "pre": 1 + 4 + 2 * 11 + 2 + 4 = 33 launches; stage "post": 1 + 14 + 1 + 2 + 2 = 20.
+
+The modules' own ``forward`` is inference only and refuses a call that wants gradients.  The differentiable forwards are functions
+of layers/train_fn.py, as for the sampler and the aggregator: ``train_fn.confidence_range_predictor(predictor, raw_cost, samples)``
+and ``train_fn.deeppruner_processor(processor, stage, left, right, samples, min_feature, max_feature)``, with gradients for both
+feature maps, the samples, the range features and every parameter (the 5x5 convolutions on ``train_fn.small_conv5x5``: weight
+gradient = plan form 6 of csrc/wgrad.hip, data gradient = the forward kernel on mirrored weights;
+docs/design/21-deeppruner-processor-backward.md)."""
 import torch.nn as nn
 
 from .... import ops, ops_deeppruner

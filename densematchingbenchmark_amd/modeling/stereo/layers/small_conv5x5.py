@@ -2,7 +2,9 @@
 convolutions (cost_processors/DeepPruner.py:69-78,180-183: Conv2d with a bias, ReLU) and the three N -> N feature convolutions
 (:80-84,184-188: ``conv_bn_relu``, layers/basic_layers.py:102-119) on 1 .. 16 channels.  Same Sequential keys as the reference
 (``0.*`` the convolution, ``1.*`` the BatchNorm if there is one); each forward is ONE launch of dmb_conv2d_k5_small_f32 with the
-bias or the eval-mode BatchNorm folded into the epilogue (fold_batch_norm).  Inference only."""
+bias or the eval-mode BatchNorm folded into the epilogue (fold_batch_norm).  The module's own ``forward`` is inference only; the
+differentiable forward is ``train_fn.small_conv5x5(unit, x)`` (the same kernel for the raw convolution and, on mirrored weights, for
+the data gradient; plan form 6 of csrc/wgrad.hip for the weight gradient)."""
 import torch
 import torch.nn as nn
 
@@ -26,6 +28,7 @@ class SmallConv5x5(nn.Sequential):
             layers.append(nn.ReLU(inplace=True))
         super().__init__(*layers)
         self.has_bn, self.has_relu = bool(batch_norm), bool(relu)
+        self.in_planes, self.out_planes = in_planes, out_planes      # (what the unit skeleton of layers/train_fn.py reads)
 
     def train(self, mode=True):
         epoch_on_mode_switch(self, mode)

@@ -1031,6 +1031,164 @@ def deeppruner_aggregator(aggregator, raw_cost):
         return [_SingleBackwardFn.apply(cost, "deeppruner_aggregator").squeeze(1)]
 
 
+# ---------------------------------------------------------------------------------------------- DeepPruner's cost processor
+class SmallConv5x5Fn(torch.autograd.Function):
+    """y = act(BN(conv5x5(x) + bias)) of one SmallConv5x5 unit (stride 1, padding 2, 1 .. 16 channels) on the unit skeleton.  Raw
+    convolution: dmb_conv2d_k5_small_f32 with the bias as its shift and no ReLU; BatchNorm2d by batch statistics, running statistics
+    or none, following its own ``training`` flag.  Backward: the weight gradient is plan form 6 of csrc/wgrad.hip; the data gradient
+    is the forward kernel on mirrored, channel-exchanged weights (stride 1 with padding 2 is its own adjoint geometry)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, skip, unit, relu, carry_x=False, carry_skip=False):
+        x_in = x
+        x = x.contiguous()
+        w = weight.detach().contiguous()
+        raw = ops_deeppruner.conv2d_k5_small(x, w, None, bias.detach().contiguous() if bias is not None else None, False)
+        return _unit_forward_tail(ctx, unit, raw, x, w, x_in, gamma, beta, bias, skip, relu, carry_x, carry_skip)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        _refuse_double_backward("SmallConv5x5")
+        dc, dx_acc, x, w, bn_grads = _unit_backward_head(ctx, grads)
+        dw = dx = None
+        if ctx.needs_input_grad[1]:
+            dw = ops.conv2d_wgrad(x, dc, 5, 1)
+        if ctx.needs_input_grad[0]:
+            dx = ops_deeppruner.conv2d_k5_small(dc, w.flip(2, 3).transpose(0, 1).contiguous())
+            if dx_acc is not None:
+                dx = dx + dx_acc
+        return _unit_backward_tail(ctx, dx, dw, bn_grads)
+
+
+def small_conv5x5(unit, x):
+    """Differentiable forward of a SmallConv5x5 (whose own ``forward`` stays inference only)."""
+    _refuse_cpu("small_conv5x5", x)
+    return _apply_carried(SmallConv5x5Fn, unit, x, None, unit.has_relu)
+
+
+class SoftArgminSampledFn(torch.autograd.Function):
+    """disp = sum_d softmax(cost)_d * sample_d over per-pixel samples (alpha = 1, normalised): cost, sample [B, D, H, W] ->
+    [B, 1, H, W].  Forward: dmb_soft_argmin_sampled_f32.  Backward, composed of torch ops on the device (D <= 14 planes; its share
+    of the step is in docs/design/21): with p = softmax(cost, 1), d_cost = d_disp * p * (sample - disp), d_sample = d_disp * p."""
+
+    @staticmethod
+    def forward(ctx, cost, sample, normalize=True):
+        if not normalize:
+            raise NotImplementedError("SoftArgminSampledFn: only the normalised form (softmax over the samples) has a backward")
+        cost, sample = cost.contiguous(), sample.contiguous()
+        disp = ops.soft_argmin_sampled(cost, sample, 1.0, True)
+        ctx.save_for_backward(cost, sample, disp)
+        return disp
+
+    @staticmethod
+    def backward(ctx, ddisp):
+        _refuse_double_backward("soft_argmin_sampled")
+        cost, sample, disp = ctx.saved_tensors
+        gp = torch.softmax(cost, 1) * ddisp
+        d_cost = gp * (sample - disp) if ctx.needs_input_grad[0] else None
+        return d_cost, (gp if ctx.needs_input_grad[1] else None), None
+
+
+class DeepPrunerVolumeFn(torch.autograd.Function):
+    """ops_deeppruner.deeppruner_volume under autograd: [B, 2C + 1 + 2P, D, H, W] = cat(fast_cat_fms(left, right, sample), sample,
+    min_feature on every plane, max_feature on every plane).  Backward, a composition: the first 2C channels through the sampled
+    volume's adjoint (dmb_fast_fms_bwd_f32, which wants them dense: one copy), the sample channel added to the sampler's column
+    derivative, the range features' gradients summed over the planes in ascending plane order."""
+
+    @staticmethod
+    def forward(ctx, left, right, sample, min_feature, max_feature):
+        left, right, sample = left.contiguous(), right.contiguous(), sample.contiguous()
+        vol = ops_deeppruner.deeppruner_volume(left, right, sample, min_feature, max_feature)
+        ctx.save_for_backward(left, right, sample)
+        ctx.P = 0 if min_feature is None else min_feature.shape[1]
+        return vol
+
+    @staticmethod
+    def backward(ctx, dvol):
+        _refuse_double_backward("deeppruner_volume")
+        left, right, sample = ctx.saved_tensors
+        need, C, P, D = ctx.needs_input_grad, left.shape[1], ctx.P, sample.shape[1]
+        dL = dR = dS = dmin = dmax = None
+        if need[0] or need[1] or need[2]:
+            dL, dR, dS = ops.fast_fms_bwd(left, right, sample, dvol[:, :2 * C].contiguous(), wrt_samples=need[2])
+        if need[2]:
+            dS = dS + dvol[:, 2 * C]
+
+        def over_planes(c0):
+            acc = dvol[:, c0:c0 + P, 0].clone()
+            for d in range(1, D):                       # ascending plane order
+                acc += dvol[:, c0:c0 + P, d]
+            return acc
+        if P and need[3]:
+            dmin = over_planes(2 * C + 1)
+        if P and need[4]:
+            dmax = over_planes(2 * C + 1 + P)
+        return dL if need[0] else None, dR if need[1] else None, dS, dmin, dmax
+
+
+def _check_volume_inputs(what, left, right, sample):
+    if left.dim() != 4 or sample.dim() != 4:
+        raise ValueError("%s: features [B, C, H, W] and per-pixel samples [B, D, H, W] expected, got %s and %s"
+                         % (what, tuple(left.shape), tuple(sample.shape)))
+    if left.shape[-1] > FAST_FMS_BWD_MAX_W:   # refuse here, not inside backward(): the adjoint keeps 2 x 8 rows of W floats in LDS
+        raise NotImplementedError("%s under autograd: feature maps wider than %d columns have no backward on the HIP path (the "
+                                  "forward alone has no such limit: run it under torch.no_grad())" % (what, FAST_FMS_BWD_MAX_W))
+
+
+def deeppruner_volume(left, right, sample, min_feature=None, max_feature=None):
+    """Differentiable ``ops_deeppruner.deeppruner_volume``: gradients for the two feature maps, the per-pixel samples and the two
+    range feature maps."""
+    _check_volume_inputs("deeppruner_volume", left, right, sample)
+    _refuse_cpu("deeppruner_volume", left, right, sample, min_feature, max_feature)
+    return DeepPrunerVolumeFn.apply(left, right, sample.float(), min_feature, max_feature)
+
+
+def confidence_range_predictor(predictor, raw_cost, disparity_sample):
+    """Differentiable forward of a ConfidenceRangePredictor (whose own ``forward`` stays inference only) -> (min_disparity,
+    max_disparity, min_disparity_feature, max_disparity_feature): the trunk, the two (hourglass, 16 -> 32, 32 -> 1) branches, two
+    soft arg-mins over the samples and the four 5x5 convolutions (DeepPruner.py:88-119).  The trunk's output and each range cost
+    have two consumers: everything runs inside one carry scope."""
+    _check_hw_volume("ConfidenceRangePredictor", raw_cost, predictor.in_planes)
+    _refuse_cpu("confidence_range_predictor", raw_cost, disparity_sample)
+    what = "confidence_range_predictor"
+    with carry_scope():
+        x = raw_cost
+        for unit in tuple(predictor.dres0) + tuple(predictor.dres1):                          # DeepPruner.py:88-89
+            x = conv_unit(unit, x, None, True)
+        costs = []
+        for branch in (predictor.min_disparity_predictor, predictor.max_disparity_predictor):  # :91-96
+            y = conv_unit(branch[1], _hw_hourglass_units(branch[0], x, None), None, True)
+            costs.append(HeadConvFn.apply(y, branch[2].weight, branch[2].bias, None).squeeze(1))
+        outs = (small_conv5x5(predictor.min_disparity_conv, SoftArgminSampledFn.apply(costs[0], disparity_sample)),   # :98-110
+                small_conv5x5(predictor.max_disparity_conv, SoftArgminSampledFn.apply(costs[1], disparity_sample)),
+                small_conv5x5(predictor.min_disparity_feature_conv, costs[0]),                                       # :112-113
+                small_conv5x5(predictor.max_disparity_feature_conv, costs[1]))
+        return tuple(_SingleBackwardFn.apply(o, what) for o in outs)
+
+
+def deeppruner_processor(processor, stage, left, right, disparity_sample, min_disparity_feature=None, max_disparity_feature=None):
+    """Differentiable forward of a DeepPrunerProcessor (whose own ``forward`` stays inference only).  Stage "pre": the volume, then
+    the range predictor's four maps; any other stage: the volume with the two range feature maps, the aggregator, the soft arg-min,
+    both up-samplings and the two 5x5 convolutions -> [disparity, disparity_feature] (DeepPruner.py:190-234).  Gradients reach
+    ``left``, ``right``, ``disparity_sample``, the two feature maps and every parameter."""
+    what = "deeppruner_processor"
+    _check_volume_inputs(what, left, right, disparity_sample)
+    if left.shape[2] % 8 or left.shape[3] % 8:
+        raise ValueError("%s: H and W must be multiples of 8 (the hourglass halves them three times), got %s" % (what, tuple(left.shape)))
+    _refuse_cpu(what, left, right, disparity_sample, min_disparity_feature, max_disparity_feature)
+    if stage == 'pre':
+        raw_cost = deeppruner_volume(left, right, disparity_sample)                                           # DeepPruner.py:192-195
+        return confidence_range_predictor(processor.confidence_range_predictor, raw_cost, disparity_sample)
+    raw_cost = deeppruner_volume(left, right, disparity_sample, min_disparity_feature, max_disparity_feature)  # :192-195, 204-208
+    cost = deeppruner_aggregator(processor.cost_aggregator, raw_cost)[0]
+    disparity = SoftArgminSampledFn.apply(cost, disparity_sample)                                             # :216-218
+    H, W = cost.shape[2:]
+    disparity = BilinearScaleFn.apply(disparity, (2 * H, 2 * W), 2.0)                                         # :221 (see the module)
+    disparity_feature = BilinearScaleFn.apply(cost, (2 * H, 2 * W), 1.0)                                      # :224
+    return [_SingleBackwardFn.apply(small_conv5x5(processor.disparity_conv, disparity), what),
+            _SingleBackwardFn.apply(small_conv5x5(processor.disparity_feature_conv, disparity_feature), what)]
+
+
 def wants_grad(module, *tensors):
     """True when a forward call must take the unit-by-unit path of this file instead of the fused inference kernels:
     (a) the module is in training mode (batch statistics and running-buffer updates are training-mode semantics with or

@@ -957,15 +957,15 @@ def deconv3d_k3s2_wgrad(x, dy):
 
 
 def conv2d_wgrad(x, dc, ksize=3, dilation=1):
-    """Weight gradient of a stride-1 nn.Conv2d (k = 1, or k = 3 with dilation 1 | 2, padding = dilation * (k // 2)):
-    x [B, Ci, H, W], dc [B, Co, H, W] -> [Co, Ci, k, k]."""
+    """Weight gradient of a stride-1 nn.Conv2d (k = 1, or k = 3 with dilation 1 | 2, padding = dilation * (k // 2); or k = 5,
+    padding 2, on 1 .. 16 input and output channels: SmallConv5x5): x [B, Ci, H, W], dc [B, Co, H, W] -> [Co, Ci, k, k]."""
     lib = _lib.load()
     x, dc = _f32c(x, "x"), _f32c(dc, "dc")
     B, Ci, H, W = x.shape
     Co = dc.shape[1]
     if tuple(dc.shape) != (B, Co, H, W):
         raise _lib.DmbLibraryError("conv2d_wgrad: dc shape %s does not match x %s" % (tuple(dc.shape), tuple(x.shape)))
-    if W % 4:
+    if W % 4 and ksize != 5:     # (the 5x5 small-channel kernel takes any width)
         # the kernel stages 16-byte units: zero columns on the right change nothing (dc is zero there, x reads as padding)
         pad = 4 - W % 4
         x, dc = torch.nn.functional.pad(x, (0, pad)), torch.nn.functional.pad(dc, (0, pad))
@@ -984,6 +984,7 @@ def conv2d_k3_wgrad(x, dc):
 
 
 WGRAD_PLAN_S1, WGRAD_PLAN_S2, WGRAD_PLAN_C1, WGRAD_PLAN_2D = 1, 2, 3, 4   # dmb_conv_wgrad_plan: the form, bits 8.. of a plan code
+WGRAD_PLAN_HW, WGRAD_PLAN_K5 = 5, 6                                       # stride (1, 2, 2); 2-D kernel 5 on 1 .. 16 channels
 
 
 def conv_wgrad_plan(kind, a, b, ksize=3, dilation=1, ncu=0):

@@ -640,7 +640,10 @@ int dmb_conv3d_k3s2_wgrad_f32(const float* small, const float* big, float* dw, f
 /* Weight gradient of a stride-1 nn.Conv2d with kernel 1, or kernel 3 with dilation 1 | 2 | 4 | 8 (padding = dilation * (k / 2)):
  * AcfNet's confidence heads (cmn/cmn.py:21-36) and the stride-1 layers of the 2-D networks.  x [B, Ci, H, W],
  * dc [B, Co, H, W] -> dw [Co, Ci, k*k].  W a multiple of 4, tensors 16-byte aligned.  The data gradient is dmb_conv2d_f32 on
- * mirrored, channel-exchanged weights.  workspace: dmb_conv2d_wgrad_workspace_floats(Co, Ci) floats. */
+ * mirrored, channel-exchanged weights.  workspace: dmb_conv2d_wgrad_workspace_floats(Co, Ci) floats.
+ * Kernel 5 with dilation 1 (padding 2) on 1 .. DMB_CONV2D_K5_MAX_C input and output channels -- DeepPruner's 5x5 heads,
+ * dmb_conv2d_k5_small_f32 -- is taken too: dw [Co, Ci, 25], any H, W >= 1, any width, operands 4-byte aligned, the same workspace;
+ * its data gradient is dmb_conv2d_k5_small_f32 on mirrored, channel-exchanged weights. */
 long long dmb_conv2d_wgrad_workspace_floats(int Co, int Ci);
 int dmb_conv2d_wgrad_f32(const float* x, const float* dc, float* dw, float* workspace, int B, int Ci, int Co, int H, int W,
                          int ksize, int dilation, void* stream);
@@ -661,10 +664,13 @@ int dmb_conv2d_wgrad_f32(const float* x, const float* dc, float* dw, float* work
  *   form 4  2-D, strips of 64 columns walked along y:  0 .. 3 = kernel 3 with dilation 1, 2, 4, 8;  4 = kernel 1
  *   form 5  DMB_WGRAD_S2 with Db == D >= 2 (stride (1, 2, 2)), tiles of 4 x 8 voxels of the small operand walked along z in segments of
  *           one plane or more:  0 / 1 = 16-byte / dword staging (dword: either width % 4 != 0 or align < 16)
+ *   form 6  DMB_WGRAD_2D with ksize 5, dilation 1 and 1 .. DMB_CONV2D_K5_MAX_C channels on both sides (decided before the width and
+ *           alignment rule of form 4, which it does not have):  0 = tiles of 8 rows x 32 columns, one thread per (co, ci) pair with its
+ *           25 taps in registers.  detail: column tiles, 1, 8 (a tile's rows), row tiles; a slot's partial result is Co x Ci x 25 floats
  * or -DMB_EINVAL / -DMB_EUNSUPPORTED where the launch would be refused with that code (dmb_last_error() then names the reason).
  * detail_host: NULL, or 6 host ints that receive the rest of the plan: tiles along x, tiles along y (2-D: the row classes = the dilation),
  * planes (2-D: rows of a class) per segment, segments (form 3: 1 and D), workgroup slots per channel block (grid x; form 3: the
- * workgroups), 32 x 32 channel blocks (grid y).  items = B x tiles x segments; slots x blocks x taps x 1024 floats (form 3: slots x Ci x 27) never
+ * workgroups), 32 x 32 channel blocks (grid y).  items = B x tiles x segments; slots x blocks x taps x 1024 floats (form 3: slots x Ci x 27; form 6: slots x Co x Ci x 25) never
  * exceed dmb_*_wgrad_workspace_floats(Co, Ci). */
 #define DMB_WGRAD_S1 1
 #define DMB_WGRAD_S2 2
