@@ -21,7 +21,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # by operation: no fused multiply-adds there (the 5x5 convolution of deeppruner_heads.hip writes its fmaf chain out)
 EXTRA_FLAGS = {"warp_volume.hip": ["-ffp-contract=off"], "spn.hip": ["-ffp-contract=off"], "patch_match.hip": ["-ffp-contract=off"],
                "deeppruner_heads.hip": ["-ffp-contract=off"]}
-SHARED_HEADERS = ["dmb_common.h", "conv3d_mfma.h", "deconv3d_plan.h", "conv2d_plan.h", "wgrad_plan.h", "interp.h", "warp_taps.h", "bilinear_hp.h", "loss_terms.h"]
+SHARED_HEADERS = ["dmb_common.h", "conv3d_mfma.h", "deconv3d_plan.h", "conv2d_plan.h", "wgrad_plan.h", "upsample_plan.h", "interp.h", "warp_taps.h", "bilinear_hp.h", "loss_terms.h"]
 
 
 def _hipcc():

@@ -6,6 +6,7 @@
 // Each kernel reads its large operand once; nothing the size of the [B, D, H, W] cost volume is written.
 #include "dmb_common.h"
 #include "interp.h"
+#include "upsample_plan.h"
 
 #pragma clang fp contract(off)
 
@@ -245,26 +246,15 @@ __global__ __launch_bounds__(256) void upsample_regress_bwd_hw_kernel(const floa
   const int xl = blockIdx.x * 256 + threadIdx.x;
   if (xl >= Wi) return;
   const int yl = blockIdx.y % Hi, zi = blockIdx.y / Hi, b = blockIdx.z;
-  auto range = [](int i, float scale, int out, int& lo, int& hi) {
-    if (scale <= 0.f) {   // a single output position blends input 0 only
-      lo = 0;
-      hi = i == 0 ? out - 1 : -1;
-      return;
-    }
-    lo = (int)floorf((float)(i - 1) / scale) - 1;
-    hi = (int)ceilf((float)(i + 1) / scale) + 1;
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > out - 1 ? out - 1 : hi;
-  };
   int ylo, yhi, xlo, xhi;
-  range(yl, sh, Ho, ylo, yhi);
-  range(xl, sw, Wo, xlo, xhi);
+  gather_range(yl, sh, Ho, ylo, yhi);
+  gather_range(xl, sw, Wo, xlo, xhi);
   const float* tb = t + ((size_t)b * Di + zi) * Ho * Wo;
   float acc = 0.f;
   // (round 5) The column weights of this thread's window do not depend on the row: they are computed ONCE (the window of a 4x
   // up-sampling is 9 .. 12 columns wide) instead of once per (row, column) -- the kernel spent its time in ~100 lerp set-ups per
   // output, not in its 100 loads (0.137 -> see profiles/r05_train_pmc.csv).  Wider windows (other scale factors) take the old loop.
-  constexpr int KMAX = 16;
+  constexpr int KMAX = UPB_KMAX;
   if (xhi - xlo < KMAX) {
     float wxs[KMAX];
 #pragma unroll
@@ -317,18 +307,12 @@ __global__ __launch_bounds__(256) void upsample_bwd_hw_rows_kernel(const float* 
                                                                    int Wi, int Ho, int Wo, float sh, float sw, int nrmax) {
   extern __shared__ float rs[];   // [nrmax][Wi]
   const int y0 = blockIdx.x * R, zi = blockIdx.y, b = blockIdx.z;
-  auto range = [](int i, float scale, int out, int& lo, int& hi) {   // (scale > 0: the launcher's condition)
-    lo = (int)floorf((float)(i - 1) / scale) - 1;
-    hi = (int)ceilf((float)(i + 1) / scale) + 1;
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > out - 1 ? out - 1 : hi;
-  };
   int glo, ghi, tmp;
-  range(y0, sh, Ho, glo, tmp);
-  range(min(y0 + R - 1, Hi - 1), sh, Ho, tmp, ghi);
+  gather_range(y0, sh, Ho, glo, tmp);
+  gather_range(min(y0 + R - 1, Hi - 1), sh, Ho, tmp, ghi);
   const int nr = min(ghi - glo + 1, nrmax);
   const float* tb = t + ((size_t)b * Di + zi) * Ho * Wo;
-  constexpr int KMAX = 16;
+  constexpr int KMAX = UPB_KMAX;
   const int RL = Wi >= 256 ? 1 : 256 / Wi;          // row lanes: threads (rl, xl)
   const int XW = Wi >= 256 ? 256 : Wi;
   const int rl = threadIdx.x / XW, xc = threadIdx.x - rl * XW;
@@ -336,7 +320,7 @@ __global__ __launch_bounds__(256) void upsample_bwd_hw_rows_kernel(const float* 
     const int xl = xb + xc;
     if (rl < RL && xl < Wi) {
       int xlo, xhi;
-      range(xl, sw, Wo, xlo, xhi);
+      gather_range(xl, sw, Wo, xlo, xhi);
       float wxs[KMAX];
 #pragma unroll
       for (int k = 0; k < KMAX; ++k) {
@@ -376,7 +360,7 @@ __global__ __launch_bounds__(256) void upsample_bwd_hw_rows_kernel(const float* 
     const int yl = y0 + idx / Wi, xl = idx % Wi;
     if (yl >= Hi) break;
     int ylo, yhi;
-    range(yl, sh, Ho, ylo, yhi);
+    gather_range(yl, sh, Ho, ylo, yhi);
     float acc = 0.f;
     for (int yo = ylo; yo <= yhi; ++yo) {
       const Lerp ly = lerp_setup(yo, Hi, sh);
@@ -388,23 +372,22 @@ __global__ __launch_bounds__(256) void upsample_bwd_hw_rows_kernel(const float* 
   }
 }
 
-// Launch of the (y, x) contraction: the row-group form where it applies (both scales > 0, column windows of fewer than 16
-// outputs, the group's row sums within 64 KB of LDS), else one thread per low-resolution voxel.
-static void launch_upsample_bwd_hw(const float* t, float* dx, int B, int planes, int Hi, int Wi, int Ho, int Wo, float sh, float sw,
+// Launch of the (y, x) contraction the plan names (upsample_plan.h): the row-group form where it applies, else one thread per
+// low-resolution voxel.
+static void launch_upsample_bwd_hw(const UpsampleBwdPlan& p, const float* t, float* dx, int planes, int Hi, int Wi, int Ho, int Wo,
                                    hipStream_t st) {
-  constexpr int R = 8;
-  if (sh > 0.f && sw > 0.f && Hi >= 2 && Wi >= 2) {
-    const int win = (int)ceilf(2.f / sw) + 5;                 // columns a low-resolution pixel may blend (bound of xhi - xlo + 1)
-    const int nrmax = (int)ceilf((float)(R + 1) / sh) + 6;    // rows a group of R may blend (bound of ghi - glo + 1)
-    const size_t lds = (size_t)nrmax * Wi * sizeof(float);
-    if (win <= 16 && lds <= 64 * 1024 && cdiv(Hi, R) <= 65535 && planes <= 65535) {
-      hipLaunchKernelGGL((upsample_bwd_hw_rows_kernel<R>), dim3(cdiv(Hi, R), planes, B), dim3(256), lds, st, t, dx, planes, Hi, Wi, Ho, Wo,
-                         sh, sw, nrmax);
-      return;
-    }
-  }
-  hipLaunchKernelGGL(upsample_regress_bwd_hw_kernel, dim3(cdiv(Wi, 256), planes * Hi, B), dim3(256), 0, st, t, dx, planes, Hi, Wi, Ho, Wo,
-                     sh, sw);
+  const dim3 grid(p.gx, p.gy, p.gz);
+  if (p.code == UPB_ROWS)
+    hipLaunchKernelGGL((upsample_bwd_hw_rows_kernel<UPB_R>), grid, dim3(256), (size_t)p.lds, st, t, dx, planes, Hi, Wi, Ho, Wo, p.sh, p.sw,
+                       p.nrmax);
+  else
+    hipLaunchKernelGGL(upsample_regress_bwd_hw_kernel, grid, dim3(256), 0, st, t, dx, planes, Hi, Wi, Ho, Wo, p.sh, p.sw);
+}
+
+static int bwd_plan_or_fail(int entry, int B, int planes, int Hi, int Wi, int Do, int Ho, int Wo, UpsampleBwdPlan* p) {
+  const char* why = "";
+  const int e = upsample_bwd_plan({entry, B, planes, Hi, Wi, Do, Ho, Wo, false}, p, &why);
+  return e ? fail(e, why) : DMB_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -534,20 +517,9 @@ __global__ __launch_bounds__(256) void avgpool2d_bwd_kernel(const float* __restr
 __global__ __launch_bounds__(64) void bilinear_ac_bwd_small_kernel(const float* __restrict__ t, float* __restrict__ dx, int C, int Hi,
                                                                    int Wi, int Ho, int Wo, float sh, float sw) {
   const int xl = blockIdx.x % Wi, yl = blockIdx.x / Wi, c = blockIdx.y, b = blockIdx.z;
-  auto range = [](int i, float scale, int out, int& lo, int& hi) {
-    if (scale <= 0.f) {
-      lo = 0;
-      hi = i == 0 ? out - 1 : -1;
-      return;
-    }
-    lo = (int)floorf((float)(i - 1) / scale) - 1;
-    hi = (int)ceilf((float)(i + 1) / scale) + 1;
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > out - 1 ? out - 1 : hi;
-  };
   int ylo, yhi, xlo, xhi;
-  range(yl, sh, Ho, ylo, yhi);
-  range(xl, sw, Wo, xlo, xhi);
+  gather_range(yl, sh, Ho, ylo, yhi);
+  gather_range(xl, sw, Wo, xlo, xhi);
   const float* tb = t + ((size_t)b * C + c) * Ho * Wo;
   const int nx = xhi - xlo + 1, total = (yhi - ylo + 1) * (nx > 0 ? nx : 0);
   float acc = 0.f;
@@ -661,18 +633,18 @@ extern "C" int dmb_soft_argmin_bwd_f32(const float* cost, const float* disp, con
 extern "C" int dmb_trilinear_ac_soft_argmin_bwd_f32(const float* x, const float* disp, const float* grad_disp, const float* grad_y,
                                                     float* scratch, float* grad_x, int B, int Di, int Hi, int Wi, int Do, int Ho,
                                                     int Wo, float alpha, const float* disp_sample_host, void* stream) {
-  if (!x || !disp || !grad_disp || !scratch || !grad_x || B <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0)
-    return fail(DMB_EINVAL, "trilinear_soft_argmin_bwd: bad argument");
-  if (Ho > 65535 || (long long)Di * Hi > 65535 || B > 65535) return fail(DMB_EUNSUPPORTED, "trilinear_soft_argmin_bwd: grid too large");
+  if (!x || !disp || !grad_disp || !scratch || !grad_x) return fail(DMB_EINVAL, "trilinear_soft_argmin_bwd: bad argument");
+  UpsampleBwdPlan p;
+  if (int e = bwd_plan_or_fail(UPB_TRILINEAR_AC_SOFT_ARGMIN, B, Di, Hi, Wi, Do, Ho, Wo, &p)) return e;
   DispVal dv;
   if (int e = fill_val(disp_sample_host, Do, dv)) return e;
   hipStream_t st = (hipStream_t)stream;
-  const float sd = ac_scale(Di, Do), sh = ac_scale(Hi, Ho), sw = ac_scale(Wi, Wo);
+  const float sd = ac_scale(Di, Do);
   hipLaunchKernelGGL(upsample_regress_bwd_z_kernel, dim3(cdiv(Wo, 256), Ho, B), dim3(256), 0, st, x, disp, grad_disp, scratch, Di, Hi,
-                     Wi, Do, Ho, Wo, sd, sh, sw, alpha, dv);
+                     Wi, Do, Ho, Wo, sd, p.sh, p.sw, alpha, dv);
   if (grad_y)   // a loss on the volume as well: its z fold joins the regression's before the (y, x) contraction
     hipLaunchKernelGGL(upsample_bwd_z_kernel, dim3(cdiv(Wo, 256), Ho, B), dim3(256), 0, st, grad_y, scratch, Di, Do, Ho, Wo, sd, 1);
-  launch_upsample_bwd_hw(scratch, grad_x, B, Di, Hi, Wi, Ho, Wo, sh, sw, st);
+  launch_upsample_bwd_hw(p, scratch, grad_x, Di, Hi, Wi, Ho, Wo, st);
   return launch_status("trilinear_soft_argmin_bwd launch failed");
 }
 
@@ -694,14 +666,27 @@ extern "C" int dmb_deconv3d_k8s4_c1_bwd_f32(const float* x, const float* w, cons
 
 extern "C" int dmb_trilinear_ac_bwd_f32(const float* grad_y, float* scratch, float* grad_x, int B, int Di, int Hi, int Wi, int Do,
                                         int Ho, int Wo, void* stream) {
-  if (!grad_y || !scratch || !grad_x || B <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0)
-    return fail(DMB_EINVAL, "trilinear_bwd: bad argument");
-  if (Ho > 65535 || (long long)Di * Hi > 65535 || B > 65535) return fail(DMB_EUNSUPPORTED, "trilinear_bwd: grid too large");
+  if (!grad_y || !scratch || !grad_x) return fail(DMB_EINVAL, "trilinear_bwd: bad argument");
+  UpsampleBwdPlan p;
+  if (int e = bwd_plan_or_fail(UPB_TRILINEAR_AC, B, Di, Hi, Wi, Do, Ho, Wo, &p)) return e;
   hipStream_t st = (hipStream_t)stream;
-  const float sd = ac_scale(Di, Do), sh = ac_scale(Hi, Ho), sw = ac_scale(Wi, Wo);
-  hipLaunchKernelGGL(upsample_bwd_z_kernel, dim3(cdiv(Wo, 256), Ho, B), dim3(256), 0, st, grad_y, scratch, Di, Do, Ho, Wo, sd, 0);
-  launch_upsample_bwd_hw(scratch, grad_x, B, Di, Hi, Wi, Ho, Wo, sh, sw, st);
+  hipLaunchKernelGGL(upsample_bwd_z_kernel, dim3(cdiv(Wo, 256), Ho, B), dim3(256), 0, st, grad_y, scratch, Di, Do, Ho, Wo, ac_scale(Di, Do), 0);
+  launch_upsample_bwd_hw(p, scratch, grad_x, Di, Hi, Wi, Ho, Wo, st);
   return launch_status("trilinear_bwd launch failed");
+}
+
+extern "C" int dmb_upsample_bwd_plan(int entry, int B, int planes_or_Di, int Hi, int Wi, int Do, int Ho, int Wo, int ncu, int* detail_host) {
+  (void)ncu;   // no adjoint form depends on the compute units (the argument keeps the two queries alike)
+  const char* why = "";
+  UpsampleBwdPlan p;
+  const int e = upsample_bwd_plan({entry, B, planes_or_Di, Hi, Wi, Do, Ho, Wo, true}, &p, &why);
+  set_last_error(why);
+  if (e) return -e;
+  if (detail_host) {
+    const int detail[6] = {p.nrmax, p.lds, (int)p.gx, (int)p.gy, (int)p.gz, p.threads};
+    for (int k = 0; k < 6; ++k) detail_host[k] = detail[k];
+  }
+  return p.code;
 }
 
 extern "C" int dmb_avgpool2d_bwd_f32(const float* grad_y, float* grad_x, int B, int C, int H, int W, int k, void* stream) {
@@ -713,15 +698,14 @@ extern "C" int dmb_avgpool2d_bwd_f32(const float* grad_y, float* grad_x, int B, 
 }
 
 extern "C" int dmb_bilinear_ac_bwd_f32(const float* grad_y, float* grad_x, int B, int C, int Hi, int Wi, int Ho, int Wo, void* stream) {
-  if (!grad_y || !grad_x || B <= 0 || C <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0) return fail(DMB_EINVAL, "bilinear_bwd: bad argument");
-  if ((long long)C * Hi > 65535 || B > 65535 || C > 65535) return fail(DMB_EUNSUPPORTED, "bilinear_bwd: grid too large");
-  if ((long long)Hi * Wi * 64 <= (long long)Ho * Wo) {   // footprints of >= 64 output pixels: one wave per input element
-    hipLaunchKernelGGL(bilinear_ac_bwd_small_kernel, dim3(Hi * Wi, C, B), dim3(64), 0, (hipStream_t)stream, grad_y, grad_x, C, Hi, Wi, Ho,
-                       Wo, ac_scale(Hi, Ho), ac_scale(Wi, Wo));
-    return launch_status("bilinear_bwd launch failed");
-  }
-  // the (y, x) contraction of the up-sampling backward, one "plane" per channel
-  launch_upsample_bwd_hw(grad_y, grad_x, B, C, Hi, Wi, Ho, Wo, ac_scale(Hi, Ho), ac_scale(Wi, Wo), (hipStream_t)stream);
+  if (!grad_y || !grad_x) return fail(DMB_EINVAL, "bilinear_bwd: bad argument");
+  UpsampleBwdPlan p;
+  if (int e = bwd_plan_or_fail(UPB_BILINEAR_AC, B, C, Hi, Wi, 0, Ho, Wo, &p)) return e;
+  if (p.code == UPB_WAVE)   // footprints of >= 64 output pixels: one wave per input element
+    hipLaunchKernelGGL(bilinear_ac_bwd_small_kernel, dim3(p.gx, p.gy, p.gz), dim3(64), 0, (hipStream_t)stream, grad_y, grad_x, C, Hi, Wi, Ho,
+                       Wo, p.sh, p.sw);
+  else   // the (y, x) contraction of the up-sampling backward, one "plane" per channel
+    launch_upsample_bwd_hw(p, grad_y, grad_x, C, Hi, Wi, Ho, Wo, (hipStream_t)stream);
   return launch_status("bilinear_bwd launch failed");
 }
 

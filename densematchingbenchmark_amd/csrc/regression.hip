@@ -8,6 +8,7 @@
 // AcfNet.py:55-57,81-83, data/datasets/evaluation/stereo/pixel_error.py:6-73.
 #include "dmb_common.h"
 #include "interp.h"
+#include "upsample_plan.h"
 
 // No implicit fma contraction in this file: the interpolation index/weight arithmetic must round exactly like the
 // reference's (ATen CPU) float code -- src = scale * dst rounded, THEN lambda = src - floor(src) -- or lambda moves
@@ -640,34 +641,38 @@ extern "C" int dmb_local_soft_argmin_f32(const float* cost, float* disp, long lo
   return launch_status("local_soft_argmin launch failed");
 }
 
-// Row form or flat form of trilinear_zcol_kernel (see the kernel): flat wherever rows are 16-byte multiples.  Measured inside
-// the PSMNet step, forms alternated in one process (scripts/ab_step.py, development option 22): 544 x 960 (240 of a row block's 256
-// lanes busy) 27.05 ms with the row form against 26.94 flat; 384 x 1248 (312 of 512) 26.60 against 26.24.
-static int trilinear_flat(int Ho, int Wo) {
-  if ((Wo & 3) != 0 || (long long)Ho * (Wo / 4) >= 0x7fffff00LL) return 0;
-  if (DMB_OPT(22)) return DMB_OPT(22) == 2;   // (development option 22: 1 = row form, 2 = flat form)
-  return 1;
+// Shape checks, kernel, layout and grid of the four up-sampling entry points below: upsample_plan.h.  An entry point checks its
+// pointers, plans, and launches what the plan names.
+static int plan_or_fail(int entry, int B, int Di, int Hi, int Wi, int Do, int Ho, int Wo, UpsamplePlan* p) {
+  const char* why = "";
+  const int e = upsample_plan({entry, B, Di, Hi, Wi, Do, Ho, Wo, 0}, p, &why);
+  return e ? fail(e, why) : DMB_OK;
+}
+
+extern "C" int dmb_upsample_plan(int entry, int B, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int ncu, int* detail_host) {
+  const char* why = "";
+  UpsamplePlan p;
+  const int e = upsample_plan({entry, B, Di, Hi, Wi, Do, Ho, Wo, ncu}, &p, &why);
+  set_last_error(why);
+  if (e) return -e;
+  if (detail_host) {
+    const int detail[7] = {p.nx, p.flat, p.zsplit, (int)p.gx, (int)p.gy, (int)p.gz, p.threads};
+    for (int k = 0; k < 7; ++k) detail_host[k] = detail[k];
+  }
+  return p.code;
 }
 
 extern "C" int dmb_trilinear_ac_f32(const float* x, float* y, int B, int Di, int Hi, int Wi, int Do, int Ho, int Wo,
                                     void* stream) {
-  if (!x || !y || B <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0)
-    return fail(DMB_EINVAL, "trilinear: bad argument");
-  if ((long long)cdiv(cdiv(Wo, 4), 256) * Do * Ho > 0x7fffffffLL || B > 65535)
-    return fail(DMB_EUNSUPPORTED, "trilinear: grid too large");
+  if (!x || !y) return fail(DMB_EINVAL, "trilinear: bad argument");
+  UpsamplePlan p;
+  if (int e = plan_or_fail(UP_TRILINEAR_AC, B, Di, Hi, Wi, Do, Ho, Wo, &p)) return e;
   hipStream_t st = (hipStream_t)stream;
-  if (Ho <= 65535 && B <= 65535) {
-    const int flat = trilinear_flat(Ho, Wo);
-    const long long nxb = flat ? ((long long)Ho * (Wo / 4) + 255) / 256 : cdiv(cdiv(Wo, 4), 256);
-    // split the plane walk only when the (row, column-block) grid alone cannot fill the chip
-    const long long nblk0 = nxb * (flat ? 1 : Ho) * B;
-    int zsplit = 1;
-    while (nblk0 * zsplit < 2048 && zsplit * 2 <= Do && zsplit < 16) zsplit *= 2;
-    hipLaunchKernelGGL(trilinear_zcol_kernel<false>, dim3((unsigned)(nxb * zsplit), flat ? 1 : Ho, B), dim3(256), 0, st, x, y, Di, Hi,
-                       Wi, Do, Ho, Wo, ac_scale(Di, Do), ac_scale(Hi, Ho), ac_scale(Wi, Wo), zsplit, (float*)nullptr, 1.f,
-                       DispVal{}, flat);
+  const dim3 grid(p.gx, p.gy, p.gz);
+  if ((p.code >> 8) == UPK_ZCOL) {
+    hipLaunchKernelGGL(trilinear_zcol_kernel<false>, grid, dim3(256), 0, st, x, y, Di, Hi, Wi, Do, Ho, Wo, ac_scale(Di, Do),
+                       ac_scale(Hi, Ho), ac_scale(Wi, Wo), p.zsplit, (float*)nullptr, 1.f, DispVal{}, p.flat);
   } else {
-    dim3 grid(cdiv(cdiv(Wo, 4), 256) * Do * Ho, B);
     hipLaunchKernelGGL(trilinear_kernel, grid, dim3(256), 0, st, x, y, Di, Hi, Wi, Do, Ho, Wo,
                        ac_scale(Di, Do), ac_scale(Hi, Ho), ac_scale(Wi, Wo));
   }
@@ -677,35 +682,30 @@ extern "C" int dmb_trilinear_ac_f32(const float* x, float* y, int B, int Di, int
 extern "C" int dmb_trilinear_ac_soft_argmin_f32(const float* x, float* y, float* disp, int B, int Di, int Hi, int Wi,
                                                 int Do, int Ho, int Wo, float alpha, const float* disp_sample_host,
                                                 void* stream) {
-  if (!x || !y || !disp || B <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || Do <= 0 || Ho <= 0 || Wo <= 0)
-    return fail(DMB_EINVAL, "trilinear_ac_soft_argmin: bad argument");
-  if (Ho > 65535 || B > 65535) return fail(DMB_EUNSUPPORTED, "trilinear_ac_soft_argmin: grid too large");
+  if (!x || !y || !disp) return fail(DMB_EINVAL, "trilinear_ac_soft_argmin: bad argument");
+  UpsamplePlan p;
+  if (int e = plan_or_fail(UP_TRILINEAR_AC_SOFT_ARGMIN, B, Di, Hi, Wi, Do, Ho, Wo, &p)) return e;
   DispVal dv;
   if (int e = fill_samples(disp_sample_host, Do, dv)) return e;
-  const int flat = trilinear_flat(Ho, Wo);
-  // (round 6) fewer than one wave per SIMD at four columns per thread: one column per thread -- four times the waves, each with a
-  // quarter of the per-plane arithmetic of its serial walk over the Do planes (one 256x512 map: 20 -> 12 us); same bits
-  if ((long long)B * Ho * cdiv(Wo, 4) < 4LL * 64 * num_cus() && (long long)Ho * Wo < 0x7fffff00LL) {
-    const long long nxb1 = flat ? ((long long)Ho * Wo + 255) / 256 : cdiv(Wo, 256);
-    hipLaunchKernelGGL((trilinear_zcol_kernel<true, 1>), dim3((unsigned)nxb1, flat ? 1 : Ho, B), dim3(256), 0, (hipStream_t)stream, x, y,
-                       Di, Hi, Wi, Do, Ho, Wo, ac_scale(Di, Do), ac_scale(Hi, Ho), ac_scale(Wi, Wo), 1, disp, alpha, dv, flat);
-    return launch_status("trilinear_ac_soft_argmin launch failed");
-  }
-  const long long nxb = flat ? ((long long)Ho * (Wo / 4) + 255) / 256 : cdiv(cdiv(Wo, 4), 256);
-  hipLaunchKernelGGL(trilinear_zcol_kernel<true>, dim3((unsigned)nxb, flat ? 1 : Ho, B), dim3(256), 0, (hipStream_t)stream, x, y,
-                     Di, Hi, Wi, Do, Ho, Wo, ac_scale(Di, Do), ac_scale(Hi, Ho), ac_scale(Wi, Wo), 1, disp, alpha, dv, flat);
+  const dim3 grid(p.gx, p.gy, p.gz);
+  if (p.nx == 1)
+    hipLaunchKernelGGL((trilinear_zcol_kernel<true, 1>), grid, dim3(256), 0, (hipStream_t)stream, x, y, Di, Hi, Wi, Do, Ho, Wo,
+                       ac_scale(Di, Do), ac_scale(Hi, Ho), ac_scale(Wi, Wo), 1, disp, alpha, dv, p.flat);
+  else
+    hipLaunchKernelGGL(trilinear_zcol_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, y, Di, Hi, Wi, Do, Ho, Wo,
+                       ac_scale(Di, Do), ac_scale(Hi, Ho), ac_scale(Wi, Wo), 1, disp, alpha, dv, p.flat);
   return launch_status("trilinear_ac_soft_argmin launch failed");
 }
 
 extern "C" int dmb_trilinear_soft_argmin_f32(const float* x, float* disp, int B, int Di, int Hi, int Wi, int Do,
                                              int Ho, int Wo, float alpha, const float* disp_sample_host,
                                              void* stream) {
-  if (!x || !disp || B <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0)
-    return fail(DMB_EINVAL, "trilinear_soft_argmin: bad argument");
+  if (!x || !disp) return fail(DMB_EINVAL, "trilinear_soft_argmin: bad argument");
+  UpsamplePlan p;
+  if (int e = plan_or_fail(UP_TRILINEAR_SOFT_ARGMIN, B, Di, Hi, Wi, Do, Ho, Wo, &p)) return e;
   DispVal dv;
   if (int e = fill_samples(disp_sample_host, Do, dv)) return e;
-  dim3 grid(cdiv(Wo, 256), Ho, B);
-  hipLaunchKernelGGL(trilinear_soft_argmin_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, disp, Di, Hi, Wi, Do,
+  hipLaunchKernelGGL(trilinear_soft_argmin_kernel, dim3(p.gx, p.gy, p.gz), dim3(256), 0, (hipStream_t)stream, x, disp, Di, Hi, Wi, Do,
                      Ho, Wo, ac_scale(Di, Do), ac_scale(Hi, Ho), ac_scale(Wi, Wo), alpha, dv);
   return launch_status("trilinear_soft_argmin launch failed");
 }
@@ -842,19 +842,17 @@ using namespace dmb;
 
 extern "C" int dmb_deconv3d_k8s4_c1_soft_argmin_f32(const float* x, const float* w, float* y, float* disp, int B, int D, int H,
                                                     int W, float alpha, const float* disp_sample_host, void* stream) {
-  if (!x || !w || !y || B <= 0 || D <= 0 || H <= 0 || W <= 0) return fail(DMB_EINVAL, "deconv_k8s4_soft_argmin: bad argument");
-  if (4 * H > 65535 || B > 65535) return fail(DMB_EUNSUPPORTED, "deconv_k8s4_soft_argmin: grid too large");
-  // a row's W threads in cdiv(W, 256) workgroups of equal size, rounded up to whole waves (312 input columns: 2 x 192 threads
-  // instead of 256 + 56 of 256)
-  const int nwg = cdiv(W, 256), wgt = cdiv(cdiv(W, nwg), 64) * 64;
-  dim3 grid(nwg, 4 * H, B);
+  if (!x || !w || !y) return fail(DMB_EINVAL, "deconv_k8s4_soft_argmin: bad argument");
+  UpsamplePlan p;   // (the workgroup size: see the plan)
+  if (int e = plan_or_fail(disp ? UP_K8S4_SOFT_ARGMIN : UP_K8S4, B, D, H, W, 4 * D, 4 * H, 4 * W, &p)) return e;
+  const dim3 grid(p.gx, p.gy, p.gz);
   if (disp) {
     DispVal dv;
     if (int e = fill_samples(disp_sample_host, 4 * D, dv)) return e;
-    hipLaunchKernelGGL(deconv_k8s4_zcol_kernel<true>, grid, dim3(wgt), 0, (hipStream_t)stream, x, w, y, disp, D, H, W, alpha, dv);
+    hipLaunchKernelGGL(deconv_k8s4_zcol_kernel<true>, grid, dim3(p.threads), 0, (hipStream_t)stream, x, w, y, disp, D, H, W, alpha, dv);
   } else {
     DispVal dv = {};
-    hipLaunchKernelGGL(deconv_k8s4_zcol_kernel<false>, grid, dim3(wgt), 0, (hipStream_t)stream, x, w, y, disp, D, H, W, alpha, dv);
+    hipLaunchKernelGGL(deconv_k8s4_zcol_kernel<false>, grid, dim3(p.threads), 0, (hipStream_t)stream, x, w, y, disp, D, H, W, alpha, dv);
   }
   return launch_status("deconv_k8s4_soft_argmin launch failed");
 }

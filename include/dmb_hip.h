@@ -56,13 +56,13 @@ extern "C" {
 
 #define DMB_MAX_DISP_SAMPLES 256 /* upper bound on the number of disparity samples D */
 
-/* ABI version: bumped whenever a signature below changes (12: dmb_conv_wgrad_plan added; 11: dmb_conv2d_plan added; 10: dmb_conv3d_k3_plan added; 9: dmb_deconv3d_k3s2_plan added; 8: dmb_bn_train_fwd_f32, dmb_catconv_pack_weights_f32, dmb_conv3d_pack_weights_multi_f32, dmb_cat_first_wgrad_maps_f32, dmb_conv3d_k3_bnstats_f32 and dmb_bn_train_act_f32 added, dmb_bn_act_bwd_f32 takes the gradient its
+/* ABI version: bumped whenever a signature below changes (13: dmb_upsample_plan and dmb_upsample_bwd_plan added; 12: dmb_conv_wgrad_plan added; 11: dmb_conv2d_plan added; 10: dmb_conv3d_k3_plan added; 9: dmb_deconv3d_k3s2_plan added; 8: dmb_bn_train_fwd_f32, dmb_catconv_pack_weights_f32, dmb_conv3d_pack_weights_multi_f32, dmb_cat_first_wgrad_maps_f32, dmb_conv3d_k3_bnstats_f32 and dmb_bn_train_act_f32 added, dmb_bn_act_bwd_f32 takes the gradient its
  * skip operand already holds (`dres_acc`); 7: DMB_CONV_SINGLE_CHAIN in the `relu` argument of the convolution
  * entry points, `flags` argument of dmb_conv3d_k3_c1_f32; 6: dmb_stereo_pad_normalize_f32 / _u8 added; 5: dmb_fast_fms_bwd_f32 takes a mode, the forward's norm and an
  * optional gradient buffer for per-pixel samples; 4: workspace argument of dmb_deconv3d_k3s2_f32, the merged-heads entry
  * points of version 3 removed).  The define is the one place the number is written: dmb_abi_version() returns it and the Python
  * binding reads it from this file. */
-#define DMB_ABI_VERSION 12
+#define DMB_ABI_VERSION 13
 int dmb_abi_version(void);
 /* Static string describing the last DMB_E* code returned on this thread ("" if none). */
 const char* dmb_last_error(void);
@@ -416,6 +416,38 @@ int dmb_trilinear_ac_soft_argmin_f32(const float* x, float* y, float* disp, int 
 int dmb_trilinear_soft_argmin_f32(const float* x, float* disp, int B, int Di, int Hi, int Wi, int Do, int Ho,
                                   int Wo, float alpha, const float* disp_sample_host, void* stream);
 
+/* What the up-sampling entry points above would launch, without launching anything: a pure function of its arguments, in the
+ * conventions of dmb_deconv3d_k3s2_plan (csrc/upsample_plan.h).  entry: which entry point --
+ *   DMB_UPSAMPLE_TRILINEAR_AC               dmb_trilinear_ac_f32
+ *   DMB_UPSAMPLE_TRILINEAR_AC_SOFT_ARGMIN   dmb_trilinear_ac_soft_argmin_f32
+ *   DMB_UPSAMPLE_TRILINEAR_SOFT_ARGMIN      dmb_trilinear_soft_argmin_f32
+ *   DMB_UPSAMPLE_K8S4                       dmb_deconv3d_k8s4_c1_soft_argmin_f32 with disp == NULL
+ *   DMB_UPSAMPLE_K8S4_SOFT_ARGMIN           dmb_deconv3d_k8s4_c1_soft_argmin_f32 with disp
+ * (the k8 / s4 entries read B and Di, Hi, Wi = D, H, W; the output is exactly 4x and Do, Ho, Wo are not read).
+ * ncu: compute units to plan for, <= 0 = the current device's (256 where there is none); only form 3 depends on them.
+ * Returns (kernel << 8) | index:
+ *   kernel 1  z-column walk, four output columns per thread (dmb_trilinear_ac_f32 with Ho <= 65535):
+ *             index = (flat layout ? 8 : 0) + log2(zsplit).  flat (Wo % 4 == 0): the (row, 4-column word) pairs of a plane are one
+ *             linear range dealt to the threads; row layout otherwise: grid y = the output row.  zsplit = 1, 2, 4, 8, 16 parts of the
+ *             plane walk: doubled while the grid has fewer than 2048 workgroups, zsplit * 2 <= Do and zsplit < 16
+ *   kernel 2  one thread per four outputs of one (plane, row) pair (dmb_trilinear_ac_f32 with Ho > 65535):  0
+ *   kernel 3  z-column walk with the soft-argmin folded in:  index = (flat ? 2 : 0) + (four columns per thread ? 1 : 0);  ONE column per
+ *             thread while B * Ho * ceil(Wo / 4) < 4 * 64 * ncu (four columns would leave less than a wave per SIMD)
+ *   kernel 4  one thread per output pixel, no volume written (dmb_trilinear_soft_argmin_f32):  0
+ *   kernel 5  k8 / s4 z-column walk:  index = (with the regression ? 4 : 0) + threads / 64 - 1;  a row's W threads in ceil(W / 256)
+ *             workgroups of equal size, rounded up to whole waves: 64, 128, 192 or 256 threads
+ * or -DMB_EINVAL / -DMB_EUNSUPPORTED where the launch would be refused with that code (dmb_last_error() then names the reason):
+ * a non-positive extent; more disparity samples (Do; k8 / s4: 4 D) than DMB_MAX_DISP_SAMPLES for the entries with a regression; a
+ * grid out of range (B > 65535; Ho > 65535 for every entry but the first; ceil(Wo / 1024) * Do * Ho > 2^31 - 1 for the first).
+ * detail_host: NULL, or 7 host ints that receive the rest of the plan: output columns per thread, flat (1) or row (0), zsplit, the
+ * grid's x, y, z, threads per workgroup. */
+#define DMB_UPSAMPLE_TRILINEAR_AC 1
+#define DMB_UPSAMPLE_TRILINEAR_AC_SOFT_ARGMIN 2
+#define DMB_UPSAMPLE_TRILINEAR_SOFT_ARGMIN 3
+#define DMB_UPSAMPLE_K8S4 4
+#define DMB_UPSAMPLE_K8S4_SOFT_ARGMIN 5
+int dmb_upsample_plan(int entry, int B, int Di, int Hi, int Wi, int Do, int Ho, int Wo, int ncu, int* detail_host);
+
 /* ------------------------------------------------------------------------------------------
  * AcfNet confidence head (cmn/cmn.py:10-36,57-69)
  *   h = relu(conv2d_3x3(cost, w1) * scale + shift)   w1: [Cm, D, 3, 3], pad 1, no bias, BN folded
@@ -763,6 +795,24 @@ int dmb_trilinear_ac_bwd_f32(const float* grad_y, float* scratch, float* grad_x,
  * backbone under training): grad_y -> grad_x. */
 int dmb_avgpool2d_bwd_f32(const float* grad_y, float* grad_x, int B, int C, int H, int W, int k, void* stream);
 int dmb_bilinear_ac_bwd_f32(const float* grad_y, float* grad_x, int B, int C, int Hi, int Wi, int Ho, int Wo, void* stream);
+
+/* Which kernel contracts the (y, x) neighbourhoods in the three adjoints of an align_corners up-sampling above, without launching
+ * anything (csrc/upsample_plan.h; the z fold before it has one form).  entry: DMB_UPSAMPLE_BWD_TRILINEAR_AC (dmb_trilinear_ac_bwd_f32),
+ * DMB_UPSAMPLE_BWD_TRILINEAR_AC_SOFT_ARGMIN (dmb_trilinear_ac_soft_argmin_bwd_f32), DMB_UPSAMPLE_BWD_BILINEAR_AC
+ * (dmb_bilinear_ac_bwd_f32: planes_or_Di = C, Do not read).  ncu is not read: no adjoint form depends on the device.  Returns
+ *   1  row groups: a workgroup contracts the output rows that 8 input rows blend into LDS row sums, then those along y -- where
+ *      both scales (in - 1) / (out - 1) are positive, Hi, Wi >= 2, the column window bound ceil(2 / sw) + 5 is at most 16 and
+ *      nrmax = ceil(9 / sh) + 6 rows of Wi floats fit 64 KiB
+ *   2  one thread per input voxel, every voxel's window of output columns narrower than 16: the register-window path throughout
+ *   3  one thread per input voxel, some window 16 columns or wider: those voxels take the general loop
+ *   4  one wave per input element (the bilinear entry with Hi * Wi * 64 <= Ho * Wo), decided before the others
+ * or -DMB_EINVAL / -DMB_EUNSUPPORTED where the launch would be refused (a non-positive extent; Do outside 1 .. DMB_MAX_DISP_SAMPLES
+ * for the entry with a regression; B, Ho or planes * Hi above 65535).
+ * detail_host: NULL, or 6 host ints: nrmax and the LDS bytes of form 1 (else 0, 0), the grid's x, y, z, threads per workgroup. */
+#define DMB_UPSAMPLE_BWD_TRILINEAR_AC 1
+#define DMB_UPSAMPLE_BWD_TRILINEAR_AC_SOFT_ARGMIN 2
+#define DMB_UPSAMPLE_BWD_BILINEAR_AC 3
+int dmb_upsample_bwd_plan(int entry, int B, int planes_or_Di, int Hi, int Wi, int Do, int Ho, int Wo, int ncu, int* detail_host);
 /* Backward of dmb_bilinear_scale_f32 (half-pixel bilinear * mult, edge_aware.py:49-50) on plain tensors. */
 int dmb_bilinear_scale_bwd_f32(const float* grad_y, float* grad_x, int B, int C, int Hi, int Wi, int Ho, int Wo, float mult,
                                void* stream);

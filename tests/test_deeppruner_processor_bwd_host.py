@@ -87,9 +87,9 @@ def test_module_refusals_are_still_in_place():
 def test_the_feature_adds_no_exported_symbol():
     """The 5x5 weight gradient is reached through dmb_conv2d_wgrad_f32, the composed backwards through existing launches."""
     names = _lib.header_symbols()
-    assert len(names) == 113 and len(set(names)) == 113
+    assert len(names) == 115 and len(set(names)) == 115   # (113 + the two up-sampling plan queries)
     assert "dmb_conv2d_wgrad_f32" in names and not any("k5" in n and "wgrad" in n for n in names)
-    assert _lib.DEFINES["DMB_ABI_VERSION"] == 12
+    assert _lib.DEFINES["DMB_ABI_VERSION"] == 13
 
 
 @pytest.mark.parametrize("name,stage,mode", Q.RUNS, ids=["%s-%s-%s" % r for r in Q.RUNS])

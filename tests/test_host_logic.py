@@ -472,8 +472,8 @@ def test_binding_constants_match_the_header():
     assert int(re.search(r"#define DMB_DECONV3D_WORKSPACE_BYTES (\d+)", text).group(1)) == _lib.DECONV3D_WORKSPACE_BYTES
     assert int(re.search(r"#define DMB_CONV_SINGLE_CHAIN (0x[0-9a-f]+)", text).group(1), 16) == _lib.CONV_SINGLE_CHAIN
     # the one place outside the header where the ABI version is written: bumping it is a conscious edit here and there
-    assert "ABI version" in text and "(12:" in text and _lib.ABI_VERSION == 12
-    assert int(re.search(r"^#define DMB_ABI_VERSION (\d+)$", text, flags=re.M).group(1)) == 12
+    assert "ABI version" in text and "(13:" in text and _lib.ABI_VERSION == 13
+    assert int(re.search(r"^#define DMB_ABI_VERSION (\d+)$", text, flags=re.M).group(1)) == 13
 
 
 def test_data_side_and_serving_api_refuse_host_tensors():
