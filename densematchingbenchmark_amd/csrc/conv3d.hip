@@ -131,10 +131,11 @@ static int conv3d_plan(const ConvDesc& d, const char** why) {
     return refuse(DMB_EUNSUPPORTED, "conv3d: 8 channels of one batch item must stay below 2 GiB (32-bit buffer offsets)");
   if ((stride == 1 || stride == 2) && (Co == 32 || Co == 64)) {
     // (round 6) launches that leave most of the chip idle: the K chain of a tile split over the eight waves of a workgroup
-    // (csrc/conv3d_sk.hip).  DMB_OPT(23) (development build): 1 = never, k >= 2 = force variant k - 1.
+    // (csrc/conv3d_sk.hip)
     int v = d.single_chain ? 0 : sk_variant(B, Ci, Co, D, H, W, stride, d.ncu);
-    if (DMB_OPT(23) == 1) v = 0;
-    if (DMB_OPT(23) >= 2) v = DMB_OPT(23) - 1;
+    // ---- development switch 23 (the release build has none): 1 = never, k >= 2 = force variant k - 1; one that the build does not
+    // hold, or whose requirements the launch misses, is declined below and the launch takes its full-grid plan
+    if (DMB_OPT(23) >= 1) v = DMB_OPT(23) - 1;
     if (v > 0 && conv3d_sk_applies(v, d)) return (CONV_SPLIT_K << 8) | (v + 4 * (stride - 1));
   }
   if (stride == 1) return conv3d_s1_plan(d, why);
@@ -163,7 +164,6 @@ extern "C" int dmb_conv3d_k3_f32(const float* x, const float* wpack, const float
   if (plan >> 8 == CONV_SPLIT_K)
     return conv3d_sk_launch((plan & 0xff) - 4 * (stride - 1), x, wpack, scale, shift, residual, y, B, Ci, Co, D, H, W, stride, relu, st);
   relu |= (DMB_OPT(6) & 0xff) << 8;                    // (development build: diagnostics, see the kernels)
-  const int relu_s1 = relu | (DMB_OPT(14) << 16);      // (development build: start-up stagger unit of the stride-1 kernels)
   if (plan >> 8 == CONV_S2) return conv3d_s2_run(plan, x, wpack, scale, shift, residual, y, B, Ci, D, H, W, relu, st);
-  return conv3d_s1_run(plan, x, wpack, scale, shift, residual, y, B, Ci, D, H, W, relu_s1, st);
+  return conv3d_s1_run(plan, x, wpack, scale, shift, residual, y, B, Ci, D, H, W, relu, st);
 }

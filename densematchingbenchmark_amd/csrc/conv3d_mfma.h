@@ -60,18 +60,17 @@ __device__ __forceinline__ void store_tile(const f32x16 (&a)[VEC], const float (
 //   CONV_S1_FLAT   stride 1, flattened dword tiles: 0 / 1 = 32 output channels, TX 60 / 52; 2 / 3 = 64 output channels
 //   CONV_S1_C128   stride 1, 128 output channels: index 0
 //   CONV_S2        stride 2: S2_ROWS1 ... below
-// (development build: indices from CONV_DEV on name the instantiations its options force)
+// (the development build's options force among these codes: it holds no instantiation of its own)
 enum { CONV_SPLIT_K = 1, CONV_S1_VEC = 2, CONV_S1_FLAT = 3, CONV_S1_C128 = 4, CONV_S2 = 5 };
 // stride-2 indices: the 64-channel tiles of the vector path (30 columns x 1 / 2 / 4 rows with the 8-byte epilogue, 22 columns x 4
 // rows, 30 x 4 with the dword epilogue), then the dword-staged 30 x 4 tile per output width
 enum { S2_ROWS1 = 0, S2_ROWS2 = 1, S2_ROWS4 = 2, S2_NARROW = 3, S2_ROWS4_DWORD = 4, S2_FLAT64 = 5, S2_FLAT32 = 6, S2_FLAT128 = 7 };
-constexpr int CONV_DEV = 0x40;
 constexpr const char* CONV3D_UNSUPPORTED = "conv3d: output channels must be 32 or 64 (or 1: dmb_conv3d_k3_c1_f32), stride 1 or 2";
 
 // csrc/conv3d_s1s2.hip: the full-grid stride-1 and stride-2 kernels behind dmb_conv3d_k3_f32.  conv3d_s1_plan / conv3d_s2_plan hold
 // every choice among their tiles and their refusals (-> the plan code, or minus the DMB_E* code with its message in *why), after
 // conv3d_plan has checked the arguments and tried the split-K form; conv3d_s1_run / conv3d_s2_run launch the planned instantiation
-// and cannot decline.  `relu` carries the development build's diagnostic bits above bit 7.
+// and cannot decline.  Both take the same `relu` word: bits 8 .. 15 carry the development build's diagnostic bits (option 6).
 int conv3d_s1_plan(const ConvDesc& d, const char** why);
 int conv3d_s2_plan(const ConvDesc& d, const char** why);
 int conv3d_s1_run(int plan, const float* x, const float* wp, const float* scale, const float* shift, const float* res, float* y, int B,

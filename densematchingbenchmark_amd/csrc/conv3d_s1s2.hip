@@ -16,11 +16,6 @@
 
 #include "conv3d_mfma.h"
 
-// Build-time experiment knob (build.py DMB_BUILD_DEFS): 0 = natural row pairs (r, r + 1) in the stride-1 kernel (see S1Cfg::GSTR).
-#ifndef DMB_S1_GSTR
-#define DMB_S1_GSTR 1
-#endif
-
 namespace dmb {
 
 // ---------------------------------------------------------------------------------------------------------
@@ -31,9 +26,10 @@ namespace dmb {
 // hourglass ([4, 64, 12, 34, 60]: 97 920 voxels = 382.5 per CU) no box tiling comes near a multiple of 256 equal workgroups (216
 // boxes of 4 x 4 x 60 = 84 % of the chip, one wave per SIMD); 64-voxel runs give 4 x 6 x 32 = 768 equal workgroups = exactly three
 // per CU, 99.6 % of their column tiles real.  The staged tile is the 3 + 2 rows a 64-voxel run can touch (W >= 32), full width.
-template <int CIN_, int COUT_, int TY_, int TX_, int CK_, int WN_, int SCHED_ = 1, int G_ = 0, int PMIN_ = 0, bool LIN_ = false>
+// (nothing reads CIN_: the kernel-name prefix S1Cfg<0, 32, 4, 48 is how scripts/summarize_profiles.py and profiles/ find the dominant layer)
+template <int CIN_, int COUT_, int TY_, int TX_, int CK_, int WN_, int G_ = 0, int PMIN_ = 0, bool LIN_ = false>
 struct S1Cfg {
-  static constexpr int CIN = CIN_, COUT = COUT_, TY = TY_, TX = TX_, CK = CK_, WN = WN_, SCHED = SCHED_;
+  static constexpr int CIN = CIN_, COUT = COUT_, TY = TY_, TX = TX_, CK = CK_, WN = WN_;
   static constexpr bool LIN = LIN_;
   static constexpr bool HEAD = false;          // S1HeadCfg: the 32 -> 1 classifier head inside the epilogue
   static constexpr int G = G_;                  // row-group width: 0 = flattened tiles, 16 = row pairs, 8 = row quads
@@ -66,10 +62,10 @@ struct S1Cfg {
   // collide and every such read takes two LDS cycles (counters of the dominant layer: 45 % of its LDS cycles were conflicts).
   // Pairing rows (r, r + 2) of a four-row tile instead -- tile q of a column = rows q and q + 2 -- puts the second row
   // 2 P = 16 (mod 32) banks on: conflict-free.  Same MFMAs on the same operands; only which accumulator holds which row changes
-  // (bit-identical: scripts/attic/kbench_s1_ab.py prints a checksum).  What it buys is LDS cycles, not time: 2.389 / 2.396 against
+  // (bit-identical by checksum; scripts/README.md, retired experiments).  What it buys is LDS cycles, not time: 2.389 / 2.396 against
   // 2.386 / 2.391 ms at [4, 32, 48, 136, 240] (noise), 2.236 / 2.240 against 2.244 / 2.243 ms at [4, 32, 48, 96, 312] (-0.3 %) --
   // the LDS pipe is a quarter busy either way and the fragment reads run a k-step ahead of their MFMAs.
-  static constexpr int GSTR = (G_ == 16 && TY_ == 4 && !LIN_ && (2 * P) % 32 == 16 && P % 32 != 16 && DMB_S1_GSTR) ? 2 : 1;
+  static constexpr int GSTR = (G_ == 16 && TY_ == 4 && !LIN_ && (2 * P) % 32 == 16 && P % 32 != 16) ? 2 : 1;
   __device__ static constexpr int row_base(int q) { return GSTR == 2 ? q : GR * q; }   // first row of the q-th group of a column
   __device__ static constexpr int lane_off(int j) { return ROWPAIR ? (j / (G_ ? G_ : 1)) * GSTR * P + (j % (G_ ? G_ : 1)) : j; }
   __device__ static constexpr int tile_off(int mt) { return ROWPAIR ? row_base(mt / XS) * P + (mt % XS) * G_ : mt * 32; }
@@ -105,7 +101,7 @@ struct S1Cfg {
 // HEAD: the 48 x 4 row-pair tile of the 32 -> 32 classifier convolution with the 32 -> 1 head that follows it (PSMNet.py:46-54)
 // inside its epilogue; see conv3d_s1_kernel.  Each workgroup leaves the head's partial sums over its own 4 x 4 x 48 voxels: a
 // 6 x 6 x 50 tile (the voxels + the one-voxel halo their taps reach), summed over overlapping tiles by conv3d_head_chain_finish_kernel.
-struct S1HeadCfg : S1Cfg<0, 32, 4, 48, 2, 1, 1, 16, 0> {
+struct S1HeadCfg : S1Cfg<0, 32, 4, 48, 2, 1, 16, 0> {
   static constexpr bool HEAD = true;
   static constexpr int OZ = TZ + 2, OY = TY + 2, OX = TX + 2;
   static constexpr int OUT_FLOATS = OZ * OY * OX;   // one workspace slot
@@ -136,16 +132,9 @@ __global__ __launch_bounds__(256, C::WPE) void conv3d_s1_kernel(const float* __r
                                                            double* __restrict__ stats) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   // development build only (DMB_DBG is the constant 0 in the release build: these branches do not exist there) -- diagnostics
-  // (option 6): 1 = no stores, 2 = no staging after the first chunk, 32 = no barrier in the chunk loop; option 14: start-up stagger
+  // (option 6): 1 = no stores, 2 = no staging after the first chunk, 32 = no barrier in the chunk loop
   const int dbg = DMB_DBG((relu >> 8) & 0xff);
-  const int stg = DMB_DBG(relu >> 16);
   relu &= 0xff;
-  if (stg > 0 && blockIdx.x < 256u * C::WPE) {
-    // the first round's workgroups of a CU start together: delay them by their slot on the CU (HW_ID.TG_ID) x stg x 3.4 us so that
-    // set-up and epilogue of one fall under the matrix work of the others (scripts/attic/s1_stagger_probe.py: -0.3 % at best)
-    const int n = (int)(__builtin_amdgcn_s_getreg((3 << 11) | (16 << 6) | 4) & 15u) * stg;   // HW_REG_HW_ID bits 19:16
-    for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(127);
-  }
   int t = xcd_remap(blockIdx.x, gridDim.x);
   const int tile = t;         // (HEAD: the workspace slot)
   const int tx = t % ntx;     // LIN: ntx = 64-voxel runs per plane, nty = 1
@@ -255,7 +244,7 @@ __global__ __launch_bounds__(256, C::WPE) void conv3d_s1_kernel(const float* __r
 #pragma unroll
     for (int ks = 0; ks < C::NK; ++ks) {
       if (ks + 1 < C::NK) load_frag(ks + 1, af[(ks + 1) & 1], bf[(ks + 1) & 1]);
-      if (C::SCHED != 0) __builtin_amdgcn_sched_barrier(0);  // keep the next step's LDS reads ahead of this step's MFMAs
+      __builtin_amdgcn_sched_barrier(0);  // keep the next step's LDS reads ahead of this step's MFMAs
 #pragma unroll
       for (int mt = 0; mt < C::MT; ++mt)
 #pragma unroll
@@ -267,7 +256,7 @@ __global__ __launch_bounds__(256, C::WPE) void conv3d_s1_kernel(const float* __r
             acc[mt][nt] = DMB_MFMA(af[ks & 1][nt], bf[ks & 1][mt], acc[mt][nt]);
           }
         }
-      if (C::SCHED != 0) __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_sched_barrier(0);
     }
     if (!(dbg & 32)) __syncthreads();  // the compiler drains the DMA (vmcnt(0)) here: next buffer complete, current one free
   };
@@ -627,12 +616,7 @@ static int launch_s1(const float* x, const float* wp, const float* scale, const 
   const int ntx = C::LIN ? cdiv(H * W, 64) : cdiv(W, C::TX), nty = C::LIN ? 1 : cdiv(H, C::TY), ntz = cdiv(D, C::TZ);
   const long long nblk = (long long)B * ntx * nty * ntz;
   if (nblk > 0x7fffffffLL) return fail(DMB_EUNSUPPORTED, "conv3d: grid too large");
-  // (development option 17: extra KB of LDS per workgroup -- fewer workgroups per CU, for occupancy experiments)
-  const size_t lds = (size_t)C::LDS_FLOATS * sizeof(float) + (size_t)DMB_OPT(17) * 1024;
-  if (DMB_OPT(17)) {   // the experiment raises the cap itself (DMB_ENSURE_LDS sets it once, to the kernel's own need)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_s1_kernel<C, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3d_s1_kernel<C, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
+  const size_t lds = (size_t)C::LDS_FLOATS * sizeof(float);
   if (res) {
     DMB_ENSURE_LDS((&conv3d_s1_kernel<C, true>), (size_t)(lds));
     hipLaunchKernelGGL((conv3d_s1_kernel<C, true>), dim3((unsigned)nblk), dim3(256), lds, st, x, wp, scale, shift, res, y, Ci, D,
@@ -697,9 +681,8 @@ static double s1_cost(const S1Tile& t, int B, int D, int H, int W, int ncu) {
   // at 256x512 / D 64, 544x960 and 384x1248) -- the estimate ranks them as measured.
   return (double)cdiv_ll(n, ncu) * (t.mt + 0.1) / t.eff;
 }
-// index of the cheapest candidate (ties: the earlier one); DMB_OPT(19) = k > 0 forces candidate k - 1 (development build)
+// index of the cheapest candidate (ties: the earlier one)
 static int s1_pick(const S1Tile* cand, const bool* ok, int n, int B, int D, int H, int W, int ncu) {
-  if (DMB_OPT(19) > 0 && DMB_OPT(19) <= n && ok[DMB_OPT(19) - 1]) return DMB_OPT(19) - 1;
   int best = -1;
   double bc = 0.0;
   for (int i = 0; i < n; ++i) {
@@ -721,8 +704,8 @@ static int flat_tx(int W) {
 // row pairs (16 columns x 2 rows per 32-voxel column tile) of 48 or 32 columns x 4 rows, row quads (8 x 4) of 24 columns x 8
 // rows; one z-slice per wave, three workgroups per CU each
 // (8-row quads stage a quarter more halo rows per byte of output and store 32-byte instead of 64-byte runs: 0.972)
-using S1Tiles32 = std::tuple<S1Cfg<0, 32, 4, 48, 2, 1, 1, 16, 0>, S1Cfg<0, 32, 8, 24, 2, 1, 1, 8, 40>, S1Cfg<0, 32, 4, 32, 2, 1, 1, 16, 0>,
-                             S1Cfg<0, 32, 2, 32, 2, 1, 1, 16, 0>>;
+using S1Tiles32 = std::tuple<S1Cfg<0, 32, 4, 48, 2, 1, 16, 0>, S1Cfg<0, 32, 8, 24, 2, 1, 8, 40>, S1Cfg<0, 32, 4, 32, 2, 1, 16, 0>,
+                             S1Cfg<0, 32, 2, 32, 2, 1, 16, 0>>;
 constexpr double S1Eff32[4] = {1.0, 0.972, 1.0, S1_EFF_32x2};
 // the fused head (S1HeadCfg) is candidate 0 with another epilogue: its workspace has one slot per workgroup of that tile
 constexpr int S1_HEAD_PICK = 0;
@@ -735,7 +718,7 @@ static int s1_pick32(int B, int D, int H, int W, int ncu) {
   int pick = s1_pick(cand.data(), ok, 4, B, D, H, W, ncu);
   // (round 6) a launch of at most ONE 32 x 4 workgroup per CU: two 32 x 2 workgroups per CU instead, so that one's prologue and
   // epilogue fall under the other's multiply phase ([1, 32, 16, 64, 128]: 57.6 -> 55.7 us, profiles/r06_sk_probe_midsizes.log)
-  if (pick == 2 && DMB_OPT(19) == 0 && (long long)B * cdiv(D, 4) * cdiv(H, 4) * cdiv(W, 32) <= ncu) pick = 3;
+  if (pick == 2 && (long long)B * cdiv(D, 4) * cdiv(H, 4) * cdiv(W, 32) <= ncu) pick = 3;
   return pick;
 }
 static long long s1_blocks32(int pick, int B, int D, int H, int W) {
@@ -752,67 +735,51 @@ static long long s1_blocks32(int pick, int B, int D, int H, int W) {
 // small images: 62 -> 37 us at [1, 64, 8, 32, 64], 59 -> 33 us at [1, 64, 4, 16, 32]); twice the halo per output of the quads
 // (round 6: chunks of four input channels for this tile -- a chunk of two is 27 MFMAs per wave between two barriers, less than
 // the copies' round trip: [1, 64, 8, 32, 64] 33.5 -> 31.6 us, [1, 64, 12, 34, 60] 59.6 -> 56.0 us; two workgroups per CU)
-using S1Tiles64 = std::tuple<S1Cfg<0, 64, 3, 64, 2, 2, 1, 16, 0, true>, S1Cfg<0, 64, 4, 40, 2, 2, 1, 8, 56>, S1Cfg<0, 64, 4, 24, 2, 2, 1, 8, 40>,
-                             S1Cfg<0, 64, 4, 32, 2, 2, 1, 8, 40>, S1Cfg<0, 64, 2, 16, 4, 2, 1, 16, 0>>;
+using S1Tiles64 = std::tuple<S1Cfg<0, 64, 3, 64, 2, 2, 16, 0, true>, S1Cfg<0, 64, 4, 40, 2, 2, 8, 56>, S1Cfg<0, 64, 4, 24, 2, 2, 8, 40>,
+                             S1Cfg<0, 64, 4, 32, 2, 2, 8, 40>, S1Cfg<0, 64, 2, 16, 4, 2, 16, 0>>;
 constexpr double S1Eff64[5] = {1.0, 1.0, 1.0, 1.0, 0.95};
+// the runs (candidate 0) take rows of 32 .. 64 voxels and planes of whole 16-byte words; `runs` = false: the box tiles only
+static bool s1_runs_ok(int H, int W) { return W >= 32 && W <= 64 && (H * W) % 4 == 0; }
+static int s1_pick64(int B, int D, int H, int W, int ncu, bool runs) {
+  static constexpr auto cand = s1_tiles<S1Tiles64>(S1Eff64, std::make_index_sequence<5>{});
+  const bool ok[5] = {runs && s1_runs_ok(H, W), true, true, true, true};
+  return s1_pick(cand.data(), ok, 5, B, D, H, W, ncu);
+}
 
 // f(C{}) for the instantiation a stride-1 plan code names: the one place where a code becomes a type, for the plan's own
 // workgroup count and for the launch
 template <class F>
 static auto s1_form(int plan, F&& f) {
   const int form = plan >> 8, k = plan & 0xff;
-#ifdef DMB_DEV
-  if (form == CONV_S1_FLAT && k == CONV_DEV) return f(S1Cfg<0, 32, 4, 60, 2, 1, 0, 0>{});
-  // (round 6 experiment) chunks of 4 input channels for the 32-column tiles
-  if (form == CONV_S1_VEC && k == CONV_DEV) return f(S1Cfg<0, 32, 4, 32, 4, 1, 1, 16, 0>{});
-  if (form == CONV_S1_VEC && k == CONV_DEV + 1) return f(S1Cfg<0, 32, 2, 32, 4, 1, 1, 16, 0>{});
-  // (round 6 experiment) the 16 x 2 tile with chunks of 2 / 8 input channels (the library's: 4)
-  if (form == CONV_S1_VEC && k == CONV_DEV + 2) return f(S1Cfg<0, 64, 2, 16, 2, 2, 1, 16, 0>{});   // (the round-5 form of the tile: chunks of 2)
-  if (form == CONV_S1_VEC && k == CONV_DEV + 3) return f(S1Cfg<0, 64, 2, 16, 8, 2, 1, 16, 0>{});
-#endif
   if (form == CONV_S1_VEC) return k < 4 ? s1_visit32(k, f) : s1_visit<S1Tiles64>(k - 4, f, std::make_index_sequence<5>{});
   if (form == CONV_S1_FLAT) {
-    if (k == 0) return f(S1Cfg<0, 32, 4, 60, 2, 1, 1, 0, 0>{});
-    if (k == 1) return f(S1Cfg<0, 32, 4, 52, 2, 1, 1, 0, 0>{});
-    if (k == 2) return f(S1Cfg<0, 64, 4, 60, 2, 2, 1, 0, 0>{});
-    return f(S1Cfg<0, 64, 4, 52, 2, 2, 1, 0, 0>{});
+    if (k == 0) return f(S1Cfg<0, 32, 4, 60, 2, 1, 0, 0>{});
+    if (k == 1) return f(S1Cfg<0, 32, 4, 52, 2, 1, 0, 0>{});
+    if (k == 2) return f(S1Cfg<0, 64, 4, 60, 2, 2, 0, 0>{});
+    return f(S1Cfg<0, 64, 4, 52, 2, 2, 0, 0>{});
   }
   // CONV_S1_C128, GC-Net's deepest level: 2 waves x 2 row tiles, 2-row tiles keep the accumulators at 160 registers
-  return f(S1Cfg<0, 128, 2, 60, 2, 2, 1, 0, 0>{});
+  return f(S1Cfg<0, 128, 2, 60, 2, 2, 0, 0>{});
 }
 
 int conv3d_s1_plan(const ConvDesc& d, const char** why) {
   const int B = d.B, Co = d.Co, D = d.D, H = d.H, W = d.W;
   const bool out_small = (long long)Co * D * H * W * 4 < 0x7fffffffLL;   // the vector epilogue addresses the whole output item
   // the vector path: 16-byte rows for staging, skip operand and stores
-  const bool vec = W % 4 == 0 && d.x_align >= 16 && d.y_align >= 16 && d.res_align >= 16 && out_small && DMB_OPT(2) == 0;
-  const int flat = flat_tx(W) == 52 ? 1 : 0;
-  auto code = [](int form, int k) { return (form << 8) | k; };
-  int plan;
-  if (Co == 32) {
-    plan = vec ? code(CONV_S1_VEC, s1_pick32(B, D, H, W, d.ncu)) : code(CONV_S1_FLAT, flat);
-#ifdef DMB_DEV
-    if (vec && DMB_OPT(19) == 9) plan = code(CONV_S1_VEC, CONV_DEV + 1);
-    if (vec && DMB_OPT(19) == 8) plan = code(CONV_S1_VEC, CONV_DEV);
-    if (DMB_OPT(0) == 1) plan = code(CONV_S1_FLAT, CONV_DEV);
-#endif
-  } else if (Co == 64) {
-    if (vec) {
-      static constexpr auto cand = s1_tiles<S1Tiles64>(S1Eff64, std::make_index_sequence<5>{});
-      const bool ok[5] = {W >= 32 && W <= 64 && (H * W) % 4 == 0 && DMB_OPT(13) == 0, true, true, true, true};
-      plan = code(CONV_S1_VEC, 4 + s1_pick(cand.data(), ok, 5, B, D, H, W, d.ncu));
-#ifdef DMB_DEV
-      if (DMB_OPT(19) == 7) plan = code(CONV_S1_VEC, CONV_DEV + 3);
-      if (DMB_OPT(19) == 6) plan = code(CONV_S1_VEC, CONV_DEV + 2);
-#endif
-    } else {
-      plan = code(CONV_S1_FLAT, 2 + flat);
-    }
-  } else if (Co == 128) {
-    plan = code(CONV_S1_C128, 0);
-  } else {
-    return *why = CONV3D_UNSUPPORTED, -DMB_EUNSUPPORTED;
+  const bool vec = W % 4 == 0 && d.x_align >= 16 && d.y_align >= 16 && d.res_align >= 16 && out_small;
+  if (Co != 32 && Co != 64 && Co != 128) return *why = CONV3D_UNSUPPORTED, -DMB_EUNSUPPORTED;
+  const int flat = (Co == 64 ? 2 : 0) + (flat_tx(W) == 52 ? 1 : 0);   // the flattened tile of this width
+  int form = Co == 128 ? CONV_S1_C128 : (vec ? CONV_S1_VEC : CONV_S1_FLAT), k = 0;
+  if (form == CONV_S1_VEC) k = Co == 32 ? s1_pick32(B, D, H, W, d.ncu) : 4 + s1_pick64(B, D, H, W, d.ncu, true);
+  if (form == CONV_S1_FLAT) k = flat;
+  // ---- development switches (the release build has none): the one place where they act on a stride-1 plan
+  if (form == CONV_S1_VEC) {
+    const int first = Co == 32 ? 0 : 4, n = Co == 32 ? 4 : 5, force = DMB_OPT(19);   // 19 = k: candidate k - 1 of the list in play
+    if (force > 0 && force <= n && (first + force - 1 != 4 || s1_runs_ok(H, W))) k = first + force - 1;
+    if (DMB_OPT(13) && k == 4) k = 4 + s1_pick64(B, D, H, W, d.ncu, false);   // 13: boxes instead of runs
+    if (DMB_OPT(2)) form = CONV_S1_FLAT, k = flat;                             // 2: flattened tiles
   }
+  const int plan = (form << 8) | k;
   const long long nblk = s1_form(plan, [&](auto c) {
     using C = decltype(c);
     return (long long)B * (C::LIN ? cdiv(H * W, 64) : cdiv(W, C::TX) * cdiv(H, C::TY)) * cdiv(D, C::TZ);
@@ -822,8 +789,8 @@ int conv3d_s1_plan(const ConvDesc& d, const char** why) {
 }
 
 int conv3d_s1_run(int plan, const float* x, const float* wpack, const float* scale, const float* shift, const float* residual, float* y,
-                  int B, int Ci, int D, int H, int W, int relu_s1, hipStream_t st) {
-  return s1_form(plan, [&](auto c) { return launch_s1<decltype(c)>(x, wpack, scale, shift, residual, y, B, Ci, D, H, W, relu_s1, st); });
+                  int B, int Ci, int D, int H, int W, int relu, hipStream_t st) {
+  return s1_form(plan, [&](auto c) { return launch_s1<decltype(c)>(x, wpack, scale, shift, residual, y, B, Ci, D, H, W, relu, st); });
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1119,12 +1086,6 @@ using S2Narrow = S2Cfg<0, 64, 4, 22, 2, 2, true>;
 // f(C{}) for the instantiation a stride-2 plan index names (conv3d_mfma.h: S2_ROWS1 ...)
 template <class F>
 static auto s2_form(int k, F&& f) {
-#ifdef DMB_DEV
-  // (round 6 experiment) chunks of 4 input channels; A/B: four-wave workgroups
-  if (k == CONV_DEV) return f(S2Cfg<0, 64, 1, 30, 4, 2, true, 1, true>{});
-  if (k == CONV_DEV + 1) return f(S2Cfg<0, 64, 2, 30, 4, 2, true, 2, true>{});
-  if (k == CONV_DEV + 2) return f(S2Cfg<0, 64, 4, 30, 2, 2, true>{});
-#endif
   if (k == S2_ROWS1) return f(S2Rows1{});
   if (k == S2_ROWS2) return f(S2Rows2{});
   if (k == S2_ROWS4) return f(S2Rows4{});
@@ -1137,7 +1098,7 @@ static auto s2_form(int k, F&& f) {
 
 static int s2_pick(const ConvDesc& d) {
   const int B = d.B, Co = d.Co, D = d.D, H = d.H, W = d.W;
-  const bool v16 = W % 4 == 0 && d.x_align >= 16 && !DMB_OPT(3);   // 16-byte aligned input rows
+  const bool v16 = W % 4 == 0 && d.x_align >= 16;   // 16-byte aligned input rows
   if (Co == 64 && v16) {
     // output positions computed per tile row: 32 with 30-column tiles, 24 with 22-column ones; the narrower tile wins at
     // the training-crop widths (Wo = 64: 3 x 96 against 3 x 128 positions per 4 rows, Wo = 32: 2 x 96 against 2 x 128)
@@ -1157,25 +1118,17 @@ static int s2_pick(const ConvDesc& d) {
     const double c_old = (double)cdiv_ll(nz * (narrow ? cdiv(Wo, 22) : cdiv(Wo, 30)) * cdiv(Ho, 4), ncu) * (narrow ? 3.0 / 0.85 : 4.0);
     const double c_two = (double)cdiv_ll(nz * cdiv(Wo, 30) * cdiv(Ho, 2), ncu) * 2.0 / 0.97;
     const double c_one = (double)cdiv_ll(nz * cdiv(Wo, 30) * Ho, ncu) * 1.0 / 0.94;
-    int rows = 4;   // of the 30-column tile; DMB_OPT(10) (development build): 3 / 4 = one- / two-row tiles whatever the estimate says
-    if (pair_ok && DMB_OPT(10) == 0) rows = (c_one < c_two && c_one < c_old) ? 1 : (c_two < c_old ? 2 : 4);
-#ifdef DMB_DEV
-    if (pair_ok && DMB_OPT(10) == 3) rows = 1;
-    if (pair_ok && DMB_OPT(10) == 4) rows = 2;
-    // (round 6 experiment) chunks of 4 input channels
-    if (pair_ok && DMB_OPT(10) == 5) return CONV_DEV;
-    if (pair_ok && DMB_OPT(10) == 6) return CONV_DEV + 1;
-#endif
-    if (rows == 1) return S2_ROWS1;
-    if (rows == 2) return S2_ROWS2;
-    if (narrow) return S2_NARROW;
-#ifdef DMB_DEV
-    if (DMB_OPT(10) == 1)   // A/B: four-wave workgroups
-      return CONV_DEV + 2;
-#endif
-    if (pair_ok && DMB_OPT(10) != 2)   // (A/B: 10 = 2 keeps the dword epilogue)
-      return S2_ROWS4;
-    return S2_ROWS4_DWORD;
+    int rows = 4;   // of the 30-column tile
+    if (pair_ok) rows = (c_one < c_two && c_one < c_old) ? 1 : (c_two < c_old ? 2 : 4);
+    const int four = narrow ? S2_NARROW : (pair_ok ? S2_ROWS4 : S2_ROWS4_DWORD);
+    int k = rows == 1 ? S2_ROWS1 : (rows == 2 ? S2_ROWS2 : four);
+    // ---- development switches (the release build has none): the one place where they act on a stride-2 plan
+    const int tile = DMB_OPT(10);   // 10: 2 = four-row tiles with the dword epilogue, 3 / 4 = one- / two-row tiles, whatever the estimate says
+    if (tile == 2) k = narrow ? S2_NARROW : S2_ROWS4_DWORD;
+    if (tile == 3 && pair_ok) k = S2_ROWS1;
+    if (tile == 4 && pair_ok) k = S2_ROWS2;
+    if (DMB_OPT(3)) k = S2_FLAT64;   // 3: dword staging
+    return k;
   }
   return Co == 64 ? S2_FLAT64 : (Co == 32 ? S2_FLAT32 : (Co == 128 ? S2_FLAT128 : -1));
 }

@@ -290,26 +290,16 @@ static constexpr long long sk_lds_bytes(int Ci) {
   return (a > b ? a : b) * 4;
 }
 
-// variant: 1 = 16 x 2 voxel tile, one 32-channel row tile per workgroup; 2 = 32 x 2 voxels, one row tile; 3 = 32 x 2 voxels, both row
-// tiles of a 64-channel layer (32 input channels only: the A fragments of a wave must fit its registers).
+// variant: 1 = 16 x 2 voxel tile, one 32-channel row tile per workgroup; 3 (stride 2) = 32 x 2 voxels, both row tiles of a 64-channel
+// layer (32 input channels only: the A fragments of a wave must fit its registers).  (2 = 32 x 2 voxels with one row tile, and the
+// stride-1 form of 3, were measured, never picked by sk_variant and are gone: profiles/r06_sk_probe.log.)
 // f(SKCfg{}) for the instantiation of (variant, stride, Co); -1 where this build holds none: the one place where a variant becomes a type.
 constexpr int SK_NW = 8;
 template <class F>
 static int sk_visit(int variant, int stride, int Co, F&& f) {
-  // (variant 2 and the stride-1 form of variant 3 are never picked by sk_variant: measured, kept in the development build only)
-  if (stride == 1) {
-    if (variant == 1) return f(SKCfg<1, SK_NW, 1, 1, 1, 4>{});
-#ifdef DMB_DEV
-    if (variant == 2) return f(SKCfg<1, SK_NW, 1, 2, 1, 4>{});
-    if (variant == 3 && Co == 64) return f(SKCfg<1, SK_NW, 2, 2, 1, 2>{});
-#endif
-  } else if (stride == 2) {
-    if (variant == 1) return f(SKCfg<2, SK_NW, 1, 1, 1, 4>{});
-#ifdef DMB_DEV
-    if (variant == 2) return f(SKCfg<2, SK_NW, 1, 2, 1, 4>{});
-#endif
-    if (variant == 3 && Co == 64) return f(SKCfg<2, SK_NW, 2, 2, 1, 2>{});
-  }
+  if (stride == 1 && variant == 1) return f(SKCfg<1, SK_NW, 1, 1, 1, 4>{});
+  if (stride == 2 && variant == 1) return f(SKCfg<2, SK_NW, 1, 1, 1, 4>{});
+  if (stride == 2 && variant == 3 && Co == 64) return f(SKCfg<2, SK_NW, 2, 2, 1, 2>{});
   return -1;
 }
 

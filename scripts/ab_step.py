@@ -1,6 +1,6 @@
 """Development aid: A/B the whole PSMNet step (bench.py's configuration) under development options, alternating the variants
 inside ONE process on ONE chip (numbers from different gpurun boxes differ by ~1 %).
-    python scripts/ab_step.py "4=1" "10=1" "4=1,10=1"      each argument: comma-separated option=value pairs of a variant"""
+    python scripts/ab_step.py "4=1" "10=2" "4=1,10=2"      each argument: comma-separated option=value pairs of a variant"""
 import os, sys
 os.environ.setdefault("DMB_LIB", "dev")   # kernel-variant switches exist only in the development build (build.py --dev)
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -67,8 +67,8 @@ with torch.no_grad():
                 _set(k, _DEFAULT.get(k, 0))
 print("# whole PSMNet step (batch 4, %dx%d, D = 192) under development options, variants alternated in one process on one chip (4 x 8 steps each);" % (_Hp, _Wp))
 print("# 13=1: narrow stride-1 planes on box tiles instead of 64-voxel runs; 4=1: deconv3d_kernel (round-2 transposed convolution) instead of "
-      "deconv3d_zy_kernel; 16=R: zy item order in groups of R tiles; 20=1: ONE class-major zy item list (round-3 order); 10=1: four-wave stride-2 "
-      "workgroups; 19=k: stride-1 tile candidate k - 1; fls=0 / 1: first-layer convolutions as five launches on one stream / on three streams; ovl=1: branch overlap; "
+      "deconv3d_zy_kernel; 16=R: zy item order in groups of R tiles; 20=1: ONE class-major zy item list (round-3 order); 10=2: stride-2 four-row tiles "
+      "with the dword epilogue; 19=k: stride-1 tile candidate k - 1; fls=0 / 1: first-layer convolutions as five launches on one stream / on three streams; ovl=1: branch overlap; "
       "hd=0: classifier branches as 32 -> 32 + 32 -> 1 launches instead of the fused head")
 for name, ts in acc.items():
     print("%-24s %s  -> min %.3f ms, median %.3f ms" % (name, " ".join("%.3f" % t for t in ts), min(ts), sorted(ts)[len(ts) // 2]))

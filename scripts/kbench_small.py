@@ -61,9 +61,8 @@ for D, H, W in ((16, 64, 128), (48, 136, 240), (48, 96, 312)):
     for name, (Ci, Co, s, sc) in (("conv1 s2 32->64 full->half", (32, 64, 2, 1)), ("conv3 s2 64->64 half->quarter", (64, 64, 2, 2))):
         f, fl = conv(Ci, Co, s, D // sc, H // sc, W // sc)
         line(name + " (library's pick)", timeit(f), fl)
-        for opt, what in ((1, "4 x 30, four waves"), (2, "4 x 30 / 4 x 22 (round 4)")):
-            lib.dmb_dev_set_option(10, opt)
-            line(name + " on " + what, timeit(f), fl)
+        lib.dmb_dev_set_option(10, 2)
+        line(name + " on 4 x 30 / 4 x 22 (round 4)", timeit(f), fl)
         lib.dmb_dev_set_option(10, 0)
     for name, sc, res in (("conv2 s1 64->64 half", 2, True), ("conv4 s1 64->64 quarter", 4, False)):
         f, fl = conv(64, 64, 1, D // sc, H // sc, W // sc, res)

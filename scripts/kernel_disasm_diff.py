@@ -1,6 +1,7 @@
 """Per-kernel comparison of the gfx950 instructions of two builds of one translation unit (no GPU needed):
-    python scripts/kernel_disasm_diff.py <parent object file> <branch object file>
-Unbundles both code objects, disassembles them and compares kernel by kernel.  Two things differ between builds whose kernels are the
+    python scripts/kernel_disasm_diff.py <parent object file> <branch object file> [<pattern>=<replacement>]
+The optional third argument is a regular-expression substitution applied to the parent's demangled kernel names before the kernels
+are paired (for a branch that renames kernels, e.g. by dropping a template parameter).  Unbundles both code objects, disassembles them and compares kernel by kernel.  Two things differ between builds whose kernels are the
 same and are left out of the comparison: the alignment padding after a kernel's last instruction, and the literal of the s_add_u32 that
 follows an s_getpc_b64 (a pc-relative distance to another symbol of the code object, which moves when any other kernel changes size)."""
 import difflib
@@ -35,12 +36,16 @@ def kernels(obj):
     return out
 
 
+def demangled(ks, rename=None):
+    names = subprocess.run(["c++filt"], input="\n".join(ks), capture_output=True, text=True).stdout.splitlines()
+    return {re.sub(rename[0], rename[1], dn) if rename else dn: ks[n] for n, dn in zip(ks, names)}
+
+
 def main():
-    a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
-    both = sorted(set(a) | set(b))
-    names = subprocess.run(["c++filt"], input="\n".join(both), capture_output=True, text=True).stdout.splitlines()
-    for n, dn in zip(both, names):
-        dn = re.sub(r"\(.*", "", dn).replace("dmb::", "").replace("void ", "")
+    a = demangled(kernels(sys.argv[1]), sys.argv[3].split("=", 1) if len(sys.argv) > 3 else None)
+    b = demangled(kernels(sys.argv[2]))
+    for n in sorted(set(a) | set(b)):
+        dn = re.sub(r"\(.*", "", n).replace("dmb::", "").replace("void ", "")
         if n not in a or n not in b:
             print("%-9s %6s   %6s   %s" % ("only in", "parent" if n in a else "", "branch" if n in b else "", dn))
             continue
