@@ -419,10 +419,12 @@ __global__ __launch_bounds__(256, C::WPE) void conv3d_s1_kernel(const float* __r
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           float4 v = *reinterpret_cast<const float4*>(my + (k * 8 + (lane >> 3)) * C::TR_PITCH + px);
-          if constexpr (STATS) {   // four voxels of one channel: FP32 inside the word, FP64 across words
+          if constexpr (STATS) {   // four voxels of one channel: summed and squared in FP64 (the square of an FP32 value is exact
+                                   // there; rounded to FP32 first, E[x^2] - mean^2 lost the variance from |mean| / std ~ 1e2 on)
             if (off0[mt] != DMA_OOB) {
-              ssum[k] += (double)((v.x + v.y) + (v.z + v.w));
-              ssq[k] += (double)fmaf(v.x, v.x, fmaf(v.y, v.y, fmaf(v.z, v.z, v.w * v.w)));
+              const double vx = (double)v.x, vy = (double)v.y, vz = (double)v.z, vw = (double)v.w;
+              ssum[k] += (vx + vy) + (vz + vw);
+              ssq[k] += fma(vx, vx, fma(vy, vy, fma(vz, vz, vw * vw)));
             }
           }
           v.x = fmaxf(fmaf(v.x, sc4[k], sh4[k]), lo2);

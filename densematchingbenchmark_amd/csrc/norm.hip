@@ -54,33 +54,26 @@ __global__ __launch_bounds__(NB) void bn_stats_kernel(const float* __restrict__ 
                                                       long long S, int nsplit, int vec) {
   __shared__ double sm[4];
   const int ch = blockIdx.y, s = blockIdx.x;
-  const float pivot = c[(long long)ch * S];
-  // FP32 lane partials over short runs, FP64 across runs
+  const double pivot = (double)c[(long long)ch * S];
+  // FP64 per lane: the difference of two FP32 values and its square are exact in FP64, so a pivot far from the mean (the corner
+  // voxel of a zero-padded post-ReLU map, an outlier) costs nothing.  FP32 lane partials lost |pivot - mean|^2 / var * 2^-24 of the
+  // variance: 1e-5 of invstd with the pivot 100 sigma away.  Cost (profiles/bn_stats_conditioning.log): none where the pass is
+  // bandwidth-bound ([4, 32, 48, 64, 128]: 38.7 us either way); at [4, 64, 24, 32, 64] a lane reads four words and reduces, the
+  // kernel is latency-bound and the FP64 conversions in front of the reduction cost 0.1 - 0.16 us of 10.9.
   double sum = 0.0, sq = 0.0;
-  float ps = 0.f, pq = 0.f;
-  int run = 0;
-  auto add = [&](float v) {
-    const float d = v - pivot;
-    ps += d;
-    pq = fmaf(d, d, pq);
-  };
-  auto flush = [&]() {
-    sum += (double)ps;
-    sq += (double)pq;
-    ps = pq = 0.f;
-    run = 0;
-  };
   for_slice(S, B, C, ch, s, nsplit, vec != 0,
             [&](long long o) {
+              // the four of a word as a tree: one dependent add per accumulator and word, not four
               const float4 v = *reinterpret_cast<const float4*>(c + o);
-              add(v.x), add(v.y), add(v.z), add(v.w);
-              if (++run == 64) flush();
+              const double d0 = (double)v.x - pivot, d1 = (double)v.y - pivot, d2 = (double)v.z - pivot, d3 = (double)v.w - pivot;
+              sum += (d0 + d1) + (d2 + d3);
+              sq += fma(d0, d0, d1 * d1) + fma(d2, d2, d3 * d3);
             },
             [&](long long o) {
-              add(c[o]);
-              if (++run == 256) flush();
+              const double d = (double)c[o] - pivot;
+              sum += d;
+              sq = fma(d, d, sq);
             });
-  flush();
   sum = norm_block_sum(sum, sm);
   sq = norm_block_sum(sq, sm);
   if (threadIdx.x == 0) {
@@ -215,7 +208,9 @@ __global__ __launch_bounds__(NB) void bn_act_train_kernel(const float* __restric
   double var = sq / n - dm * dm;
   if (var < 0.0) var = 0.0;
   // pivot_free: the partial sums come from a convolution's epilogue (conv3d_s1_kernel, STATS: FP64 sums of the raw values and
-  // their squares, no pivot -- E[x^2] - mean^2 in FP64 loses nothing an FP32 tensor could show until |mean| / std ~ 1e4)
+  // their squares, each square exact in FP64, no pivot -- E[x^2] - mean^2 loses (|mean| / std)^2 * 2^-53 of the variance: invstd
+  // within 2e-6 of FP64 at |mean| / std = 1000 (tests/test_conditioning_gpu.py), 1e-8 lost at 1e4.  With the squares rounded to FP32
+  // before the sum it was (|mean| / std)^2 * 2^-24 / sqrt(n): 1e-5 of invstd at 100, 1e-3 at 1000)
   const double mean = (pivot_free ? 0.0 : (double)c[(long long)ch * S]) + dm;
   const float invstd = (float)(1.0 / sqrt(var + (double)eps));
   const float g = gamma ? gamma[ch] : 1.f, bta = beta ? beta[ch] : 0.f;

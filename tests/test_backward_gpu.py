@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from oracle import dmb_oracle as O
+from tests._values import close as _close  # noqa: F401  (other test modules import it from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -19,14 +20,6 @@ def _ops():
 def _rand(shape, seed, scale=1.0):
     g = torch.Generator().manual_seed(seed)
     return torch.randn(shape, generator=g) * scale
-
-
-def _close(got, ref64, ref32, what, floor=2e-6):
-    """|got - FP64| must stay within 4x the FP32 oracle's own error (plus a floor, default 2e-6, of the value range)."""
-    scale = ref64.abs().max().item()
-    err = (got.double() - ref64).abs().max().item()
-    own = (ref32.double() - ref64).abs().max().item()
-    assert err <= 4 * own + floor * scale, "%s: error %.3e vs oracle FP32 error %.3e (range %.3e)" % (what, err, own, scale)
 
 
 @pytest.mark.parametrize("Ci,Co,shape", [
@@ -1185,7 +1178,9 @@ def test_batch_statistics_from_the_convolution_epilogue(dev, shape):
     """dmb_conv3d_k3_bnstats_f32 + dmb_bn_train_act_f32 (ABI 8) against the convolution followed by dmb_bn_train_fwd_f32: the raw
     output bit for bit; the partial sums against FP64 sums of that output (partial tiles in every direction are masked); mean /
     invstd / scale / shift / running buffers within 1e-6 relative (the two forms sum in a different order and the fused one has no
-    pivot) and the normalised output within 2e-6 of its range."""
+    pivot) and the normalised output within 2e-6 of its range.  The last block hands bn_train_act partials computed in torch FP64 for
+    an output moved by 300: it checks the finishing arithmetic of the pivot-free form, NOT the epilogue's own sums at a large mean --
+    tests/test_conditioning_gpu.py::test_statistics_from_the_convolution_epilogue does, through the convolution itself."""
     ops = _ops()
     B, Ci, D, H, W = shape
     x = _rand(shape, 121).to(dev)
@@ -1204,7 +1199,7 @@ def test_batch_statistics_from_the_convolution_epilogue(dev, shape):
     assert torch.equal(raw, ref_raw)
     tot = parts.sum(dim=1)
     r64 = ref_raw.double()
-    # (the four voxels of a 16-byte word are added, and squared, in FP32 before they enter the FP64 sums: 1e-7 of a word's value each)
+    # (the four voxels of a 16-byte word are added, and squared, in FP64 like the sums they enter: only the order differs from torch's)
     n = r64[:, 0].numel()
     assert torch.allclose(tot[:, 0], r64.sum(dim=(0, 2, 3, 4)), rtol=1e-7, atol=3e-7 * n ** 0.5 * float(r64.abs().max()))
     assert torch.allclose(tot[:, 1], (r64 * r64).sum(dim=(0, 2, 3, 4)), rtol=1e-6, atol=1e-6)
@@ -1217,7 +1212,7 @@ def test_batch_statistics_from_the_convolution_epilogue(dev, shape):
     for a, b, what in ((m1, m2, "mean"), (i1, i2, "invstd"), (s1, s2, "scale"), (h1, h2, "shift"), (rm1, rm2, "running_mean"), (rv1, rv2, "running_var")):
         assert (a - b).abs().max().item() <= 1e-6 * max(1.0, b.abs().max().item()) + 2e-7, what
     assert (y1 - y2).abs().max().item() <= 2e-6 * max(1.0, y1.abs().max().item())
-    # an output with a large mean: the pivot-free sums still give the variance (FP64)
+    # FP64 partials of an output with a large mean: the pivot-free FINISH still gives the variance (the sums are torch's, not the epilogue's)
     big = raw + 300.0
     parts_big = torch.stack([big.double().sum(dim=(0, 2, 3, 4)), (big.double() ** 2).sum(dim=(0, 2, 3, 4))], -1).unsqueeze(1).contiguous()
     _, mb, ib, _, _ = ops.bn_train_act(big, parts_big, None, None, None, None, None, 0.1, 1e-5, None, False)
