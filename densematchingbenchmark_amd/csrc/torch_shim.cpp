@@ -320,6 +320,7 @@ std::tuple<at::Tensor, at::Tensor, c10::optional<at::Tensor>> bn_act_bwd(const a
 }
 
 // dmb_conv2d_wgrad_f32 (autograd of the 2-D units w.r.t. their weights): x [B, Ci, H, W], dc [B, Co, H, W], W % 4 == 0
+// (any W for the small-channel 5x5 and the one-output-channel 3x3 forms, plan forms 6 and 7)
 at::Tensor conv2d_wgrad(const at::Tensor& x, const at::Tensor& dc, int64_t ksize, int64_t dilation) {
   f32(x, "x");
   f32(dc, "dc");
@@ -332,6 +333,63 @@ at::Tensor conv2d_wgrad(const at::Tensor& x, const at::Tensor& dc, int64_t ksize
                            (int)W, (int)ksize, (int)dilation, stream_of(x)),
       "dmb_conv2d_wgrad_f32");
   return dw;
+}
+
+// dmb_conv2d_pack_weights_f32: nn.Conv2d weight [Co, Ci, k, k] -> the MFMA A-fragment stream.  A training step re-packs every 2-D unit's
+// weight twice (forward, data gradient): on maps of a refinement stage the call's interpreter time is longer than the kernels around it.
+at::Tensor conv2d_pack_weights(const at::Tensor& w) {
+  f32(w, "weight");
+  if (w.dim() != 4 || w.size(2) != w.size(3)) raise("conv2d_pack_weights: weight must be [Co, Ci, k, k]");
+  const int64_t Co = w.size(0), Ci = w.size(1), k = w.size(2);
+  const long long n = dmb_conv2d_packed_floats((int)Co, (int)Ci, (int)k);
+  if (n <= 0) raise("conv2d_pack_weights: unsupported weight shape");
+  at::Tensor wp = at::empty({(int64_t)n}, w.options());
+  chk(dmb_conv2d_pack_weights_f32(w.data_ptr<float>(), wp.data_ptr<float>(), (int)Co, (int)Ci, (int)k, stream_of(w)), "dmb_conv2d_pack_weights_f32");
+  return wp;
+}
+
+// The pack of a stride-1 layer's data-gradient convolution where it is ONE launch: the layer's taps mirrored and its channel roles
+// exchanged ([Co, Ci, k, k] -> [Ci, Co, k, k]: the same three ATen calls as ops.conv2d_dgrad_packs, the same bits), packed.
+at::Tensor conv2d_dgrad_pack(const at::Tensor& w) {
+  f32(w, "weight");
+  if (w.dim() != 4) raise("conv2d_dgrad_pack: weight must be [Co, Ci, k, k]");
+  return conv2d_pack_weights(w.detach().transpose(0, 1).flip({2, 3}).contiguous());
+}
+
+// dmb_preact_conv_f32 in its plainest 2-D form -- a 3x3 stride-1 convolution with no prologue, no affine and no gate, + residual and
+// ReLU where a residual is given -- into a fresh output: the refinement head's classifier and its data gradient.
+at::Tensor preact_conv2d(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& residual) {
+  f32(x, "x");
+  f32(w, "weight");
+  if (x.dim() != 4 || w.dim() != 4 || w.size(1) != x.size(1) || w.size(2) != 3 || w.size(3) != 3) raise("preact_conv2d: x [B, Ci, H, W] with weight [Co, Ci, 3, 3]");
+  const int64_t B = x.size(0), Ci = x.size(1), H = x.size(2), W = x.size(3), Co = w.size(0);
+  at::Tensor y = at::empty({B, Co, H, W}, x.options());
+  if (residual.has_value() && residual->sizes() != y.sizes()) raise("preact_conv2d: residual shape != output shape");
+  chk(dmb_preact_conv_f32(x.data_ptr<float>(), nullptr, (int)B, w.data_ptr<float>(), nullptr, nullptr, nullptr, nullptr, optr(residual, "residual"),
+                          y.data_ptr<float>(), nullptr, nullptr, (int)B, (int)Ci, (int)Co, 1, (int)H, (int)W, 2, 1, 0, (int)Ci, 0, (int)Co, 0, stream_of(x)),
+      "dmb_preact_conv_f32");
+  return y;
+}
+
+// dmb_bilinear_scale_f32 / dmb_bilinear_scale_bwd_f32 on plain tensors (a fresh output): the two ends of the refinement head's tail
+at::Tensor bilinear_scale(const at::Tensor& x, int64_t Ho, int64_t Wo, double mult) {
+  f32(x, "x");
+  if (x.dim() != 4 || Ho < 1 || Wo < 1) raise("bilinear_scale: x must be [B, C, H, W] and the output size positive");
+  at::Tensor y = at::empty({x.size(0), x.size(1), Ho, Wo}, x.options());
+  chk(dmb_bilinear_scale_f32(x.data_ptr<float>(), y.data_ptr<float>(), (int)x.size(0), (int)x.size(1), (int)x.size(2), (int)x.size(3), (int)Ho, (int)Wo,
+                             (float)mult, (int)x.size(1), 0, stream_of(x)),
+      "dmb_bilinear_scale_f32");
+  return y;
+}
+
+at::Tensor bilinear_scale_bwd(const at::Tensor& gy, int64_t Hi, int64_t Wi, double mult) {
+  f32(gy, "grad_y");
+  if (gy.dim() != 4 || Hi < 1 || Wi < 1) raise("bilinear_scale_bwd: grad_y must be [B, C, Ho, Wo] and the input size positive");
+  at::Tensor gx = at::empty({gy.size(0), gy.size(1), Hi, Wi}, gy.options());
+  chk(dmb_bilinear_scale_bwd_f32(gy.data_ptr<float>(), gx.data_ptr<float>(), (int)gy.size(0), (int)gy.size(1), (int)Hi, (int)Wi, (int)gy.size(2),
+                                 (int)gy.size(3), (float)mult, stream_of(gy)),
+      "dmb_bilinear_scale_bwd_f32");
+  return gx;
 }
 
 void set_error_class(py::object cls) {
@@ -364,4 +422,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_train_fwd", &bn_train_fwd);
   m.def("bn_act_bwd", &bn_act_bwd);
   m.def("conv2d_wgrad", &conv2d_wgrad);
+  m.def("conv2d_pack_weights", &conv2d_pack_weights);
+  m.def("conv2d_dgrad_pack", &conv2d_dgrad_pack);
+  m.def("preact_conv2d", &preact_conv2d);
+  m.def("bilinear_scale", &bilinear_scale);
+  m.def("bilinear_scale_bwd", &bilinear_scale_bwd);
 }

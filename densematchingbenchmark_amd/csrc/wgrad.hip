@@ -516,7 +516,7 @@ __global__ __launch_bounds__(256, 4) void conv3d_c1_wgrad_kernel(const float* __
 
 // One wave per number of the result ((channel, tap)): the lanes walk the workgroups' partials 64 apart (independent loads; one thread walking all of
 // them alone was a chain of 256 .. 1024 dependent-latency loads, 63 us for 864 numbers), each in FP64, then a fixed butterfly.
-// (n = Ci x 27 numbers per workgroup; the 5x5 form below: Co x Ci x 25 per slot)
+// (n = Ci x 27 numbers per workgroup; the 5x5 form below: Co x Ci x 25 per slot; the 2-D one-channel form: Ci x 9)
 __global__ __launch_bounds__(256) void wgrad_reduce_flat_kernel(const float* __restrict__ ws, float* __restrict__ dw, int n, int nchunk) {
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (i >= n) return;
@@ -849,6 +849,114 @@ __global__ __launch_bounds__(256, Wg5Cfg::PER_CU) void conv2d_k5_wgrad_kernel(co
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// 2-D, kernel 3 with ONE output channel on 1 .. DMB_REFINE_HEAD_MAX_C input channels (plan form 7): dW[0, ci, ky, kx] =
+// sum_{b, y, x} dc[b, 0, y, x] * x[b, ci, y + ky - 1, x + kx - 1] for nn.Conv2d(Ci, 1, 3, 1, 1) -- the classifier of DeepPruner's
+// refinement head (16 -> 1).  M = 1 against N = Ci x 9 <= 144: the 32 x 32 MFMA tile of form 4 is 31 rows of zeros, and FP32 MFMA
+// runs at the vector FP32 rate anyway, so this is a VALU kernel in the manner of the 5x5 one above.  A workgroup walks tiles of
+// 8 rows x 32 columns: the haloed x tile (10 x 34 per channel) and the dc tile go to LDS with plain loads (any width, any
+// alignment, zeros outside the image).  A tile is 32 units of (row, 8 columns); a thread owns ONE channel's 9 taps in registers for
+// the whole launch and belongs to one of min(256 / Ci, 32) groups, which takes units grp, grp + groups, ...: per unit 8 dc words
+// and 3 x 10 x words from LDS for 72 FMAs.  At 16 channels the 32 lanes that share an LDS access are 16 channels x 2 rows of one
+// column segment: the channel pitch is 2 mod 32 and the row pitches are odd, so they meet 32 different banks (x) or two words
+// that 16 lanes each share (dc).  (Other channel counts are correct, not conflict-free.)  The groups' sums are added in
+// ascending group order through LDS at the end; partial results per slot [Ci][9] go to the workspace and are added over the
+// slots in FP64 in a fixed order: no atomics, bit-reproducible.
+// ------------------------------------------------------------------------------------------------------------------
+struct WgC1x2dCfg {
+  static constexpr int MAXC = DMB_REFINE_HEAD_MAX_C, KS = 3, NTAP = KS * KS;
+  static constexpr int TY = 8, TX = 32, SEG = 8, UNITS = TY * (TX / SEG);
+  static constexpr int XR = TY + 2, XW = TX + 2;                     // rows and used columns of the haloed x tile
+  static constexpr int XP = XW + 1, XC = XR * XP + 4, DP = TX + 1;   // pitches (floats): x row, x channel, dc row
+  static constexpr int PER_CU = 4;
+  static constexpr int groups(int Ci) { return 256 / Ci < UNITS ? 256 / Ci : UNITS; }
+  static constexpr int lds_floats(int Ci) {
+    const int tiles = Ci * XC + TY * DP, red = groups(Ci) * Ci * NTAP;
+    return tiles > red ? tiles : red;
+  }
+  static_assert(XP % 2 == 1 && DP % 2 == 1 && XC % 32 == 2 && XC >= XR * XP, "bank-conflict-free pitches at 16 channels");
+  static_assert(MAXC * PER_CU * NTAP <= 2 * 9 * 1024, "the slots' partial results fit the 2-D workspace");
+  static_assert((MAXC * XC + TY * DP) * 4 * PER_CU <= 160 * 1024 && 256 * NTAP * 4 * PER_CU <= 160 * 1024, "tile");
+};
+
+// An item = (batch item, tile row, tile column); nty tile rows.  workspace: ws[slot][ci][tap]
+__global__ __launch_bounds__(256, WgC1x2dCfg::PER_CU) void conv2d_c1_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dc,
+                                                                                 float* __restrict__ ws, int B, int Ci, int H, int W, int ntx,
+                                                                                 int nty) {
+  typedef WgC1x2dCfg C;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* xs = lds;
+  float* ds = lds + Ci * C::XC;
+  const int slot = xcd_remap(blockIdx.x, gridDim.x), nslots = gridDim.x;
+  const int tid = threadIdx.x;
+  const int G = C::groups(Ci);
+  const bool active = tid < G * Ci;
+  const int grp = tid / Ci, ci = tid - grp * Ci;
+  const size_t HW = (size_t)H * W;
+  const int items = B * nty * ntx;
+
+  float acc[C::NTAP];
+#pragma unroll
+  for (int t = 0; t < C::NTAP; ++t) acc[t] = 0.f;
+
+  for (int it = slot; it < items; it += nslots) {
+    const int tx = it % ntx;
+    const int r = it / ntx;
+    const int ty = r % nty, b = r / nty;
+    const int x0 = tx * C::TX, y0 = ty * C::TY;
+    const float* xb = x + (size_t)b * Ci * HW;
+    const float* db = dc + (size_t)b * HW;
+    __syncthreads();   // the previous tile is still being read by slower waves
+    for (int i = tid; i < Ci * C::XR * C::XW; i += 256) {
+      const int ch = i / (C::XR * C::XW), q = i - ch * (C::XR * C::XW);
+      const int row = q / C::XW, col = q - row * C::XW;
+      const int gy = y0 - 1 + row, gx = x0 - 1 + col;
+      xs[ch * C::XC + row * C::XP + col] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? xb[ch * HW + (size_t)gy * W + gx] : 0.f;
+    }
+    {
+      const int row = tid / C::TX, col = tid - row * C::TX;   // TY x TX = 256: one word per thread
+      const int gy = y0 + row, gx = x0 + col;
+      ds[row * C::DP + col] = (gy < H && gx < W) ? db[(size_t)gy * W + gx] : 0.f;
+    }
+    __syncthreads();
+    if (active) {
+      for (int u = grp; u < C::UNITS; u += G) {
+        const int row = u % C::TY, c0 = (u / C::TY) * C::SEG;
+        if (y0 + row >= H || x0 + c0 >= W) continue;   // (dc is zero there)
+        float dr[C::SEG];
+        const float* dp = ds + row * C::DP + c0;
+#pragma unroll
+        for (int j = 0; j < C::SEG; ++j) dr[j] = dp[j];
+#pragma unroll
+        for (int ky = 0; ky < C::KS; ++ky) {
+          float xr[C::SEG + 2];
+          const float* xp = xs + ci * C::XC + (row + ky) * C::XP + c0;
+#pragma unroll
+          for (int j = 0; j < C::SEG + 2; ++j) xr[j] = xp[j];
+#pragma unroll
+          for (int j = 0; j < C::SEG; ++j)
+#pragma unroll
+            for (int kx = 0; kx < C::KS; ++kx) acc[ky * C::KS + kx] = fmaf(dr[j], xr[j + kx], acc[ky * C::KS + kx]);
+        }
+      }
+    }
+  }
+  // the groups' results, added in ascending group order (the tiles' LDS is free now)
+  __syncthreads();
+  float* red = lds;
+  if (active) {
+#pragma unroll
+    for (int t = 0; t < C::NTAP; ++t) red[(grp * Ci + ci) * C::NTAP + t] = acc[t];
+  }
+  __syncthreads();
+  float* wsb = ws + (size_t)slot * Ci * C::NTAP;
+  for (int e = tid; e < Ci * C::NTAP; e += 256) {
+    float s = red[e];
+    for (int g = 1; g < G; ++g) s += red[g * Ci * C::NTAP + e];
+    wsb[e] = s;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // The instantiations a launch can run: ONE list per form.  Bits 0-7 of a plan code are the position in the form's list
 // (include/dmb_hip.h numbers them); wgrad_plan names a position and wg_visit is the only place where one becomes a type.
 // ------------------------------------------------------------------------------------------------------------------
@@ -978,6 +1086,13 @@ int wgrad_plan(const WgradDesc& d, WgradPlan* p, const char** why) {
       // one row class; a "segment" is a tile's rows: items = B x tiles, accumulated in registers by the slot that walks them
       return planned(WGRAD_K5, 0, ntx, 1, H, C::TY, (long long)B * ntx, wgrad_slots_per_block(Co, Ci, C::PER_CU, ncu));
     }
+    if (d.ksize == 3 && d.dilation == 1 && Co == 1 && Ci <= WgC1x2dCfg::MAXC) {   // one output channel: any width, any alignment
+      typedef WgC1x2dCfg C;
+      const int ntx = cdiv(W, C::TX);
+      if ((long long)B * ntx * cdiv(H, C::TY) > LIM) return refuse(DMB_EUNSUPPORTED, "conv2d_wgrad (1 channel): too many tiles");
+      // as kernel 5: one row class, a "segment" is a tile's rows; [slot][Ci][9] partials, four slots per CU (asserted to fit)
+      return planned(WGRAD_C1_2D, 0, ntx, 1, H, C::TY, (long long)B * ntx, wgrad_slots_per_block(Co, Ci, C::PER_CU, ncu));
+    }
     if (W % 4 != 0 || !aligned) return refuse(DMB_EUNSUPPORTED, "conv2d_wgrad: the width must be a multiple of 4 and the tensors 16-byte aligned");
     const int dil = d.ksize == 1 ? 1 : d.dilation;   // (a 1x1 layer has no dilation)
     const int index = d.ksize == 1 ? 4 : (d.ksize != 3 ? -1 : (dil == 1 ? 0 : (dil == 2 ? 1 : (dil == 4 ? 2 : (dil == 8 ? 3 : -1)))));
@@ -1073,6 +1188,13 @@ extern "C" int dmb_conv2d_wgrad_f32(const float* x, const float* dc, float* dw, 
     const int n = Co * Ci * Wg5Cfg::NTAP;
     hipLaunchKernelGGL(wgrad_reduce_flat_kernel, dim3(cdiv(n, 4)), dim3(256), 0, st, workspace, dw, n, p.slots);
     return launch_status("conv2d_wgrad (kernel 5) launch failed");
+  }
+  if (p.code >> 8 == WGRAD_C1_2D) {
+    hipLaunchKernelGGL(conv2d_c1_wgrad_kernel, dim3((unsigned)p.slots), dim3(256), WgC1x2dCfg::lds_floats(Ci) * 4, st, x, dc, workspace, B, Ci, H, W, p.ntx,
+                       p.nseg);
+    const int n = Ci * WgC1x2dCfg::NTAP;
+    hipLaunchKernelGGL(wgrad_reduce_flat_kernel, dim3(cdiv(n, 4)), dim3(256), 0, st, workspace, dw, n, p.slots);
+    return launch_status("conv2d_wgrad (1 channel) launch failed");
   }
   return wg_visit<Wg2dForms>(p.code, [&](auto c) {
     typedef decltype(c) C;

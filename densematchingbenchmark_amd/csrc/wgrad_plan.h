@@ -13,13 +13,14 @@
 
 namespace dmb {
 // the form, bits 8.. of a plan code; bits 0-7: the position in the form's list of instantiations (wgrad.hip)
-enum { WGRAD_S1 = 1, WGRAD_S2 = 2, WGRAD_C1 = 3, WGRAD_2D = 4, WGRAD_HW = 5, WGRAD_K5 = 6 };
+enum { WGRAD_S1 = 1, WGRAD_S2 = 2, WGRAD_C1 = 3, WGRAD_2D = 4, WGRAD_HW = 5, WGRAD_K5 = 6, WGRAD_C1_2D = 7 };
 
 // What the three entry points decide a launch from: no pointers, no device.
 struct WgradDesc {
   int kind;             // DMB_WGRAD_S1 (plans WGRAD_S1, or WGRAD_C1 for one output channel), DMB_WGRAD_S2 (WGRAD_S2, or WGRAD_HW
                         // where the operands have the same depth of two planes or more), DMB_WGRAD_2D (WGRAD_2D, or WGRAD_K5 for
-                        // kernel 5 on 1 .. 16 channels)
+                        // kernel 5 on 1 .. 16 channels, or WGRAD_C1_2D for kernel 3, dilation 1, one output channel, 1 .. 16 input
+                        // channels)
   int B, Co, Ci;        // channels of the operand that gives dw its rows (dc; stride 2: small) and its columns (x; stride 2: big)
   int D, H, W;          // extents of both operands; stride 2: of the small one; 2-D: D = 1
   int Db, Hb, Wb;       // stride 2: extents of the big operand
@@ -32,7 +33,7 @@ struct WgradDesc {
 struct WgradPlan {
   int code;         // (form << 8) | index
   int ntx, nty;     // tiles along x and y (2-D: column strips and row classes = the dilation)
-  int seg, nseg;    // planes (2-D: class rows; kernel 5: a tile's rows) per segment, segments (one output channel: 1, D)
+  int seg, nseg;    // planes (2-D: class rows; kernel 5 and 2-D one-channel: a tile's rows) per segment, segments (one output channel: 1, D)
   int slots, blocks;
 };
 

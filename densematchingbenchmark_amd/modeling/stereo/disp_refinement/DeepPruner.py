@@ -4,7 +4,8 @@ the reference's spelling -- and ``DeepPrunerRefinement``), same constructor argu
 Launches per stage: two copies into the guide buffer (cat(low_ref_group_fms[i], init_disp), :83), the six conv + BatchNorm + ReLU
 layers on the fused conv2d kernel (Ci -> 32, 32 -> 32, 32 -> 32, 32 -> 16 dilation 2, 16 -> 16 dilation 4, 16 -> 16) and ONE launch
 of csrc/refine_head.hip for the rest: classify (16 -> 1), + init_disp, ReLU (:40-42), * 2 and the bilinear up-sampling by two
-(:87).  Inference only."""
+(:87).  Inference only; the differentiable forward is ``train_fn.deeppruner_refinement`` (docs/design/22), which runs the six
+layers on the training units' launches and the tail as two launches with the same bits, one autograd node per stage."""
 import torch
 import torch.nn as nn
 

@@ -1189,6 +1189,137 @@ def deeppruner_processor(processor, stage, left, right, disparity_sample, min_di
             _SingleBackwardFn.apply(small_conv5x5(processor.disparity_feature_conv, disparity_feature), what)]
 
 
+# ---------------------------------------------------------------------------------------------- DeepPruner's refinement
+class RefineHeadFn(torch.autograd.Function):
+    """The tail of a refinement stage, y = up2(2 * relu(conv3x3_{Ci -> 1}(x) + init)) (disp_refinement/DeepPruner.py:40-42, 87),
+    Ci <= 16, from launches the library already has.  Forward: r = relu(conv(x) + init) on dmb_preact_conv_f32 (no prologue, the
+    residual epilogue: one ascending (ci, ky, kx) fmaf chain from 0, the chain of csrc/refine_head.hip), then
+    dmb_bilinear_scale_f32 by two -- the bits of ops_deeppruner.refine_head_up2.  Backward: the up-sampling's adjoint, the ReLU
+    mask from r (r > 0 IS conv + init > 0), d_init = dc, dx = the 1 -> Ci convolution of dc with the mirrored weight on the same
+    direct kernel, dw = plan form 7 of csrc/wgrad.hip."""
+
+    @staticmethod
+    def forward(ctx, x, weight, init):
+        x, init = x.contiguous(), init.contiguous()
+        w = weight.detach().contiguous()
+        r = ops.preact_conv(x, w, residual=init)          # (with a residual the epilogue is relu(sum + residual))
+        ctx.save_for_backward(x, w, r)
+        H, W = r.shape[2:]
+        return ops.bilinear_scale(r, (2 * H, 2 * W), 2.0)
+
+    @staticmethod
+    def backward(ctx, dy):
+        _refuse_double_backward("refinement_head")
+        x, w, r = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dr = ops.bilinear_scale_bwd(dy.contiguous(), tuple(r.shape[2:]), 2.0)
+        one, zero = _const(1.0, 1, r.device), _const(0.0, 1, r.device)
+        dc = ops.bn_act_bwd(dr, r, r, one, zero, zero, one, True, False)[0]     # dr where r > 0: the mask from the output
+        # the mirrored, channel-exchanged weight [Ci, 1, 3, 3]: with one output channel the exchange is a view of the flipped copy
+        dx = ops.preact_conv(dc, w.flip(2, 3).view(w.shape[1], 1, 3, 3)) if need[0] else None
+        dw = ops.conv2d_wgrad(x, dc, 3, 1) if need[1] else None
+        return dx, dw, (dc if need[2] else None)
+
+
+def refinement_head(block, init_disp, guide):
+    """Differentiable tail of a RefinementHeand (whose own ``forward`` stays inference only): ``guide`` is the output of the six
+    conv + BatchNorm + ReLU layers [B, Ci <= 16, H, W], ``init_disp`` [B, 1, H, W] -> [B, 1, 2H, 2W].  Gradients reach both and
+    ``block.classify.weight``."""
+    w = block.classify.weight
+    if guide.dim() != 4 or guide.shape[1] != w.shape[1] or guide.shape[1] > ops_deeppruner.REFINE_HEAD_MAX_C \
+            or tuple(init_disp.shape) != (guide.shape[0], 1) + tuple(guide.shape[2:]):
+        raise ValueError("refinement_head: guide [B, %d, H, W] and init_disp [B, 1, H, W] expected, got %s and %s"
+                         % (w.shape[1], tuple(guide.shape), tuple(init_disp.shape)))
+    _refuse_cpu("refinement_head", guide, init_disp, w)
+    return RefineHeadFn.apply(guide, w, init_disp)
+
+
+class _PlainCtx:
+    """What the static ``forward`` / ``backward`` of ``Conv2dUnitFn`` and ``RefineHeadFn`` read and write of an autograd context
+    (``needs_input_grad``, ``save_for_backward`` / ``saved_tensors``, ``set_materialize_grads``, plain attributes), for a caller
+    that runs several of them inside ONE Function.  What it keeps of autograd's saved-tensor rules: a tensor modified in place
+    between forward and backward is refused (its ``_version`` is compared, as autograd does).  What it does not: the tensors are
+    released when the owning node dies, not right after backward -- so a second backward over the same graph runs, with or
+    without ``retain_graph`` -- and ``torch.autograd.graph.saved_tensors_hooks`` (checkpointing, offload) do not see them."""
+
+    def __init__(self, needs_input_grad):
+        self.needs_input_grad, self._saved, self._versions = tuple(needs_input_grad), (), ()
+
+    def save_for_backward(self, *tensors):
+        self._saved, self._versions = tensors, tuple(None if t is None else t._version for t in tensors)
+
+    @property
+    def saved_tensors(self):
+        for t, v in zip(self._saved, self._versions):
+            if t is not None and t._version != v:
+                raise RuntimeError("one of the variables needed for gradient computation has been modified by an inplace operation: "
+                                   "a %s tensor saved by a refinement stage is at version %d, expected %d" % (tuple(t.shape), t._version, v))
+        return self._saved
+
+    def set_materialize_grads(self, flag):
+        pass
+
+
+class RefineStageFn(torch.autograd.Function):
+    """One refinement stage after its guide is built: the six conv + BatchNorm + ReLU layers and the head, as ONE node of the
+    autograd graph.  The forward is ``Conv2dUnitFn.forward`` six times and ``RefineHeadFn.forward``, the backward their
+    ``backward``s in reverse -- the same launches in the same order with the same bits as eight nodes chained through
+    ``conv2d_unit`` and ``refinement_head`` (a plain chain: no tensor inside has a second consumer, so there is nothing to carry).
+    At a 256 x 512 crop the interpreter, not the GPU, sets the stage's pace (docs/design/22), and a Python autograd node costs it
+    more than any kernel of the stage takes.  The units run on ``_PlainCtx`` objects: its docstring states what that keeps and what
+    it gives up of autograd's saved-tensor rules (tests/test_deeppruner_refinement_bwd_gpu.py pins both).  Inputs: the block (its units supply geometry and BatchNorm buffers), guide, init, per unit (weight, bias,
+    gamma, beta), the classifier's weight.  Double backward is refused before the first launch."""
+
+    @staticmethod
+    def forward(ctx, block, guide, init, *params):
+        need = ctx.needs_input_grad
+        x, ctx.units = guide, []
+        for i, unit in enumerate(block.conv):
+            c = _PlainCtx((need[1] if i == 0 else True,) + tuple(need[3 + 4 * i:7 + 4 * i]) + (False,) * 5)
+            x = Conv2dUnitFn.forward(c, x, *params[4 * i:4 * i + 4], None, unit, True)
+            ctx.units.append(c)
+        ctx.head = _PlainCtx((True, need[-1], need[2]))
+        return RefineHeadFn.forward(ctx.head, x, params[-1], init)
+
+    @staticmethod
+    def backward(ctx, dy):
+        _refuse_double_backward("deeppruner_refinement")
+        dx, d_classify, d_init = RefineHeadFn.backward(ctx.head, dy)
+        grads = ()
+        for c in reversed(ctx.units):
+            out = Conv2dUnitFn.backward(c, dx)
+            dx, grads = out[0], tuple(out[1:5]) + grads          # (dw, dbias, dgamma, dbeta) of the unit
+        return (None, dx, d_init) + grads + (d_classify,)
+
+
+def deeppruner_refinement(refinement, disps, low_ref_group_fms):
+    """Differentiable forward of a DeepPrunerRefinement (whose own ``forward`` stays inference only): per stage the guide
+    cat(low_ref_group_fms[i], init_disp) (DeepPruner.py:83), then the six conv + BatchNorm + ReLU layers and the head as one
+    ``RefineStageFn``.  Returns a new list, the incoming maps and one map per stage, reversed: the better map first.  Gradients
+    reach every ``low_ref_group_fms[i]``, the incoming disparity (the guide's last channel, the head's ``init`` and its own place in
+    the list) and every parameter.  Every BatchNorm follows its own ``training`` flag."""
+    what = "deeppruner_refinement"
+    disps = list(disps)
+    _refuse_cpu(what, *disps, *low_ref_group_fms[:refinement.num])
+    for i in range(refinement.num):
+        init_disp, fms, block = disps[-1], low_ref_group_fms[i], refinement.refine_blocks[i]
+        if fms.dim() != 4 or tuple(init_disp.shape) != (fms.shape[0], 1) + tuple(fms.shape[2:]):
+            raise ValueError("%s: stage %d takes features [B, C, H, W] and a disparity [B, 1, H, W], got %s and %s"
+                             % (what, i, tuple(fms.shape), tuple(init_disp.shape)))
+        head_in = block.classify.weight.shape[1]
+        if fms.shape[1] + 1 != block.in_planes or head_in != block.conv[-1].out_planes or head_in > ops_deeppruner.REFINE_HEAD_MAX_C:
+            raise ValueError("%s: stage %d is built for %d guide channels and a head of at most %d, got features %s"
+                             % (what, i, block.in_planes, ops_deeppruner.REFINE_HEAD_MAX_C, tuple(fms.shape)))
+        params = []
+        for unit in block.conv:                                                   # :38-39
+            conv, _, gamma, beta = _unit_params(unit)
+            params += [conv.weight, conv.bias, gamma, beta]
+        guide = torch.cat((fms, init_disp), 1)                                    # :83
+        disps.append(RefineStageFn.apply(block, guide, init_disp, *params, block.classify.weight))   # :40-42, 85-87
+    disps.reverse()
+    return disps
+
+
 def wants_grad(module, *tensors):
     """True when a forward call must take the unit-by-unit path of this file instead of the fused inference kernels:
     (a) the module is in training mode (batch statistics and running-buffer updates are training-mode semantics with or

@@ -958,14 +958,16 @@ def deconv3d_k3s2_wgrad(x, dy):
 
 def conv2d_wgrad(x, dc, ksize=3, dilation=1):
     """Weight gradient of a stride-1 nn.Conv2d (k = 1, or k = 3 with dilation 1 | 2, padding = dilation * (k // 2); or k = 5,
-    padding 2, on 1 .. 16 input and output channels: SmallConv5x5): x [B, Ci, H, W], dc [B, Co, H, W] -> [Co, Ci, k, k]."""
+    padding 2, on 1 .. 16 input and output channels: SmallConv5x5): x [B, Ci, H, W], dc [B, Co, H, W] -> [Co, Ci, k, k].  k = 3,
+    dilation 1 with one output channel on 1 .. 16 input channels (the refinement head's classifier) runs a kernel of its own."""
     lib = _lib.load()
     x, dc = _f32c(x, "x"), _f32c(dc, "dc")
     B, Ci, H, W = x.shape
     Co = dc.shape[1]
     if tuple(dc.shape) != (B, Co, H, W):
         raise _lib.DmbLibraryError("conv2d_wgrad: dc shape %s does not match x %s" % (tuple(dc.shape), tuple(x.shape)))
-    if W % 4 and ksize != 5:     # (the 5x5 small-channel kernel takes any width)
+    c1 = ksize == 3 and dilation == 1 and Co == 1 and Ci <= _lib.DEFINES["DMB_REFINE_HEAD_MAX_C"]     # plan form 7 (one output channel)
+    if W % 4 and ksize != 5 and not c1:     # (the 5x5 small-channel and the one-output-channel kernels take any width)
         # the kernel stages 16-byte units: zero columns on the right change nothing (dc is zero there, x reads as padding)
         pad = 4 - W % 4
         x, dc = torch.nn.functional.pad(x, (0, pad)), torch.nn.functional.pad(dc, (0, pad))
@@ -985,6 +987,7 @@ def conv2d_k3_wgrad(x, dc):
 
 WGRAD_PLAN_S1, WGRAD_PLAN_S2, WGRAD_PLAN_C1, WGRAD_PLAN_2D = 1, 2, 3, 4   # dmb_conv_wgrad_plan: the form, bits 8.. of a plan code
 WGRAD_PLAN_HW, WGRAD_PLAN_K5 = 5, 6                                       # stride (1, 2, 2); 2-D kernel 5 on 1 .. 16 channels
+WGRAD_PLAN_C1_2D = 7                                                      # 2-D kernel 3, one output channel, 1 .. 16 input channels
 
 
 def conv_wgrad_plan(kind, a, b, ksize=3, dilation=1, ncu=0):
@@ -1017,8 +1020,10 @@ def conv2d_dgrad_packs(w, dilation=1):
     65 .. 96 (three 32-channel tiles), at most 32 with dilation 4 | 8: [(c0, n, pack), ...]."""
     w = _f32c(w, "weight")
     Ci = w.shape[1]
-    wt = w.detach().transpose(0, 1).flip(2, 3).contiguous()           # [Ci, Co, k, k]: a convolution Co -> Ci
     cap = 32 if dilation > 2 else 128
+    if Ci <= cap and not 64 < Ci <= 96:            # one chunk: mirrored, exchanged and packed in one trip through the interpreter
+        return [(0, Ci, pack_conv2d_weights(w, dgrad=True))]
+    wt = w.detach().transpose(0, 1).flip(2, 3).contiguous()           # [Ci, Co, k, k]: a convolution Co -> Ci
     out, c0 = [], 0
     while c0 < Ci:
         n = min(cap, Ci - c0)
@@ -1275,6 +1280,9 @@ def bilinear_ac_bwd(grad_y, in_hw):
 
 
 def bilinear_scale_bwd(grad_y, in_hw, mult):
+    sh = _lib.shim()
+    if sh is not None and grad_y.dtype == torch.float32:
+        return sh.bilinear_scale_bwd(grad_y if grad_y.is_contiguous() else grad_y.contiguous(), int(in_hw[0]), int(in_hw[1]), float(mult))
     grad_y = _f32c(grad_y, "grad_y")
     B, C, Ho, Wo = grad_y.shape
     Hi, Wi = in_hw
@@ -1585,8 +1593,15 @@ def _window_ptr(t, ch_offset):
     return ctypes.c_void_p(t.data_ptr() + 4 * ch_offset * t.shape[2] * t.shape[3])
 
 
-def pack_conv2d_weights(w):
-    """nn.Conv2d weight [Co, Ci, k, k] (k in {1, 3, 5}) -> MFMA A-fragment stream."""
+def pack_conv2d_weights(w, dgrad=False):
+    """nn.Conv2d weight [Co, Ci, k, k] (k in {1, 3, 5}) -> MFMA A-fragment stream.  ``dgrad``: the pack of the layer's data-gradient
+    convolution instead, its taps mirrored and its channel roles exchanged ([Ci, Co, k, k])."""
+    sh = _lib.shim()
+    if sh is not None and w.dtype == torch.float32:
+        w = w if w.is_contiguous() else w.contiguous()
+        return sh.conv2d_dgrad_pack(w) if dgrad else sh.conv2d_pack_weights(w)
+    if dgrad:
+        w = w.detach().transpose(0, 1).flip(2, 3)
     lib = _lib.load()
     w = _f32c(w, "weight")
     Co, Ci, k = w.shape[0], w.shape[1], w.shape[2]
@@ -1694,6 +1709,9 @@ def bilinear_ac(x, out_hw, out=None, out_ch_offset=0):
 
 def bilinear_scale(x, out_hw, mult=1.0, out=None, out_ch_offset=0):
     """F.interpolate(x, out_hw, mode='bilinear', align_corners=False) * mult."""
+    sh = _lib.shim() if out is None else None
+    if sh is not None and x.dtype == torch.float32:
+        return sh.bilinear_scale(x if x.is_contiguous() else x.contiguous(), int(out_hw[0]), int(out_hw[1]), float(mult))
     x = _f32c(x, "x")
     B, C, Hi, Wi = x.shape
     Ho, Wo = out_hw
@@ -1835,6 +1853,12 @@ def preact_conv(x, w, stride=1, pool=False, pre_scale=None, pre_shift=None, pre_
     launch with the pre-activation prologue and the epilogue of dmb_preact_conv_f32.  ``in_window=(offset, Ci)`` reads channels
     [offset, offset + Ci) of x; ``x2`` (same shape as x) is a second view appended to the batch; ``out`` (optional) is a
     [B (+ B2), Ctot, (D,) Ho, Wo] tensor written at channel ``out_ch_offset``.  ``gate=True`` returns (G1, G2, G3)."""
+    sh = _lib.shim()
+    if (sh is not None and x.dim() == 4 and w.dim() == 4 and stride == 1 and x2 is None and out is None and in_window is None
+            and not (pool or pre_relu or relu or gate) and pre_scale is None and pre_shift is None and post_scale is None
+            and post_shift is None and x.dtype == w.dtype == torch.float32 and w.shape[1] <= PREACT_MAX_CI and w.shape[0] <= PREACT_MAX_CO):
+        return sh.preact_conv2d(x if x.is_contiguous() else x.contiguous(), w if w.is_contiguous() else w.contiguous(),
+                                None if residual is None else (residual if residual.is_contiguous() else residual.contiguous()))
     x = _f32c(x, "x")
     w = _f32c(w, "weight")
     ndim = x.dim() - 2

@@ -675,7 +675,9 @@ int dmb_conv3d_k3s2_wgrad_f32(const float* small, const float* big, float* dw, f
  * mirrored, channel-exchanged weights.  workspace: dmb_conv2d_wgrad_workspace_floats(Co, Ci) floats.
  * Kernel 5 with dilation 1 (padding 2) on 1 .. DMB_CONV2D_K5_MAX_C input and output channels -- DeepPruner's 5x5 heads,
  * dmb_conv2d_k5_small_f32 -- is taken too: dw [Co, Ci, 25], any H, W >= 1, any width, operands 4-byte aligned, the same workspace;
- * its data gradient is dmb_conv2d_k5_small_f32 on mirrored, channel-exchanged weights. */
+ * its data gradient is dmb_conv2d_k5_small_f32 on mirrored, channel-exchanged weights.
+ * Kernel 3 with dilation 1 and ONE output channel on 1 .. DMB_REFINE_HEAD_MAX_C input channels -- the classifier of DeepPruner's
+ * refinement head -- has a kernel of its own (plan form 7 below): any H, W >= 1, any width, operands 4-byte aligned. */
 long long dmb_conv2d_wgrad_workspace_floats(int Co, int Ci);
 int dmb_conv2d_wgrad_f32(const float* x, const float* dc, float* dw, float* workspace, int B, int Ci, int Co, int H, int W,
                          int ksize, int dilation, void* stream);
@@ -699,10 +701,15 @@ int dmb_conv2d_wgrad_f32(const float* x, const float* dc, float* dw, float* work
  *   form 6  DMB_WGRAD_2D with ksize 5, dilation 1 and 1 .. DMB_CONV2D_K5_MAX_C channels on both sides (decided before the width and
  *           alignment rule of form 4, which it does not have):  0 = tiles of 8 rows x 32 columns, one thread per (co, ci) pair with its
  *           25 taps in registers.  detail: column tiles, 1, 8 (a tile's rows), row tiles; a slot's partial result is Co x Ci x 25 floats
+ *   form 7  DMB_WGRAD_2D with ksize 3, dilation 1, ONE output channel (Co == 1) and 1 .. DMB_REFINE_HEAD_MAX_C input channels -- the
+ *           classifier of DeepPruner's refinement head (decided before the width and alignment rule of form 4, which it does not
+ *           have: any H, W >= 1, operands 4-byte aligned):  0 = tiles of 8 rows x 32 columns, one thread per input channel and group
+ *           of pixels with its 9 taps in registers.  detail: column tiles, 1, 8 (a tile's rows), row tiles; a slot's partial result
+ *           is Ci x 9 floats
  * or -DMB_EINVAL / -DMB_EUNSUPPORTED where the launch would be refused with that code (dmb_last_error() then names the reason).
  * detail_host: NULL, or 6 host ints that receive the rest of the plan: tiles along x, tiles along y (2-D: the row classes = the dilation),
  * planes (2-D: rows of a class) per segment, segments (form 3: 1 and D), workgroup slots per channel block (grid x; form 3: the
- * workgroups), 32 x 32 channel blocks (grid y).  items = B x tiles x segments; slots x blocks x taps x 1024 floats (form 3: slots x Ci x 27; form 6: slots x Co x Ci x 25) never
+ * workgroups), 32 x 32 channel blocks (grid y).  items = B x tiles x segments; slots x blocks x taps x 1024 floats (form 3: slots x Ci x 27; form 6: slots x Co x Ci x 25; form 7: slots x Ci x 9) never
  * exceed dmb_*_wgrad_workspace_floats(Co, Ci). */
 #define DMB_WGRAD_S1 1
 #define DMB_WGRAD_S2 2
